@@ -15,6 +15,11 @@ N GPUs: one process per GPU (torch.distributed.run), chains sharded by rank
 -> weak scaling.  Timing: barrier + synchronize on both sides of exactly K
 steps, max over ranks.
 
+A plain run (``--gpus N --steps K --warmup W``) sets up, warms up and times the headline alone and
+prints its result line (``roofline`` from the timed launches' own HIP events); ``--dump-outputs DIR``
+also writes the last timed step's recorded rows.  Everything else -- ESS runs, the host-streamed
+headline, the secondary lines, the CPU baseline, the detail file -- runs only with ``--full``.
+
 Extra fields: "roofline" (fp64 work of the fused sweep kernel per launch over
 its HIP-event-timed duration on the launch stream), "cpu_baseline" (the
 oracle's restatement of the reference loop, numpy/LAPACK SVD, 1 thread, on this
@@ -925,6 +930,26 @@ def write_detail(out, path=None):
         return None
 
 
+DUMP_MAX_BYTES = 48 << 20   # of the 64 MB --dump-outputs may write in all
+
+
+def dump_outputs(path, recs, rank=0, world=1):
+    """--dump-outputs: the arrays the last timed step returned -- ``recs``: name -> (sweeps, chains, k)
+    device tensor of recorded rows -- as path/<name>.npy (float64; ranks past 0 write <name>_rank<r>.npy).
+    When the records of all ranks exceed DUMP_MAX_BYTES every array keeps the same fixed sample of the
+    chains (sorted indices from a seeded generator, every sweep and column of a kept chain), so two builds
+    run with the same arguments write rows that compare one to one."""
+    os.makedirs(path, exist_ok=True)
+    C = next(iter(recs.values())).shape[1]
+    per_chain = sum(t.shape[0] * t.shape[2] * 8 for t in recs.values())
+    keep = min(C, max(1, DUMP_MAX_BYTES // world // per_chain))
+    idx = np.sort(np.random.default_rng(20251020).choice(C, keep, replace=False)) if keep < C else np.arange(C)
+    sel = torch.as_tensor(idx, dtype=torch.long, device=next(iter(recs.values())).device)
+    for name, t in recs.items():
+        a = t.index_select(1, sel).to("cpu", torch.float64).numpy()
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def launch_ranks(args_list, n):
     """`bench.py --gpus N` outside a launcher: start N ranks of this script under
     torch.distributed.run (one process per GPU, 127.0.0.1 rendezvous) and return their
@@ -1002,7 +1027,20 @@ def main():
     ap.add_argument("--c5-chains", type=int, default=16)
     ap.add_argument("--c5-steps", type=int, default=5)
     ap.add_argument("--dry-run", action="store_true", help="launcher/rendezvous check only: no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, measure everything else: ESS runs, the host-streamed headline, the "
+                         "secondary lines (--indep, --pta, --ecorr, --config5) and the CPU baseline, and write the "
+                         "detail file.  Without it only the headline is set up, warmed up and timed, and the "
+                         "options of those other legs have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (its recorded x and b "
+                         "rows, a fixed seeded sample of the chains) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline alone
+        args.ess = args.host_stream = args.indep = args.config5 = args.ecorr = 0
+        args.pta = "none"
+        args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(sys.argv[1:], args.gpus))
@@ -1087,6 +1125,8 @@ def main():
     info = run.info.cpu().numpy()
     if info.any():
         raise RuntimeError(f"{int((info != 0).sum())} chains hit a non-PD Sigma")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": x_rec, "b": b_rec}, rank, world)
 
     total_chains = C * world
     value = total_chains * K * S / el
@@ -1098,17 +1138,19 @@ def main():
     exe = executed_flops_per_chain_sweep(model.NF, int(model.nm[0])) * C * S / launch_s / 1e12
     # ESS per chain-sweep from a separate untimed run of 256 chains (same kernel, same law; gpu_ess:
     # the CPU leg's run lengths and estimator)
-    ce = min(C, 256)
-    ess_run = FreeSpectrumChains(model, 1e-18, 1e-8, ce, x0[:ce], chain_base=rank * C)
-    xe = torch.empty(S, ce, 30, dtype=torch.float64, device=dev)
+    ess_rec = None
+    if args.ess:
+        ce = min(C, 256)
+        ess_run = FreeSpectrumChains(model, 1e-18, 1e-8, ce, x0[:ce], chain_base=rank * C)
+        xe = torch.empty(S, ce, 30, dtype=torch.float64, device=dev)
 
-    def ess_block(n_max, rec):
-        n = min(S, n_max)
-        ess_run.run(n, record_b=False, x_rec=xe[:n])
-        return n, (xe[:n] if rec else None)
-    ess_rec = gpu_ess(ess_block, "single") if args.ess else None
+        def ess_block(n_max, rec):
+            n = min(S, n_max)
+            ess_run.run(n, record_b=False, x_rec=xe[:n])
+            return n, (xe[:n] if rec else None)
+        ess_rec = gpu_ess(ess_block, "single")
+        del xe, ess_run
     ess = value * ess_rec["per_chain_sweep_min_bin"] if ess_rec else None
-    del xe, ess_run
     K_sweeps = K * S
 
     host = None
@@ -1247,7 +1289,8 @@ def main():
             sec[name]["cpu_baseline"] = baseline(kind, sec[name].get("ess"))
     if rank == 0:
         out["secondary"] = sec
-        out["detail"] = write_detail(out)
+        if args.full or os.environ.get("GS_BENCH_DETAIL"):
+            out["detail"] = write_detail(out)
         print(result_line(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,4 +1,5 @@
-"""bench.py with /proc/self/maps written just before the first ECORR model is built (GS_MAPS_OUT), so
+"""bench.py (run it with --full: the ECORR lines are secondary ones) with /proc/self/maps written just
+before the first ECORR model is built (GS_MAPS_OUT), so
 a crash inside a profiler's launch hook can be mapped to (library, offset) -- the round-5 PMC SIGSEGV
  came from bench.py's ECORR line, not from a standalone ECORR run."""
 import os

@@ -5,11 +5,12 @@
 # Steps, each under its own time limit; a crash / abort / timeout ends the script (no retries):
 #   TESTS=1     pytest -m gpu (SEL= a test selection, default tests/)
 #   SMOKE=1     __graft_entry__.smoke()
-#   BENCH=1     the driver's bench command: bench.py --gpus 1 --steps 20 --warmup 5 [bench args]
+#   BENCH=1     the whole bench (every line, ESS, CPU baseline): bench.py --gpus 1 --steps 20 --warmup 5 --full [bench args]
 #   PROF=0      rocprofv3 --kernel-trace --stats of the same bench command + per-launch durations
 #               of the dominant kernels (tools/gpu_prof_trace.sh)
 #   PMC=""      kernel-name substrings: FETCH_SIZE / WRITE_SIZE / SQ passes over PMC_ARGS bench
-#               arguments, per-dispatch means (tools/gpu_pmc_traffic.sh)
+#               arguments (with --full for a secondary line's kernels), per-dispatch means
+#               (tools/gpu_pmc_traffic.sh)
 #   AB=""       library variants (csrc/Makefile variant-one) for an interleaved headline A/B
 #               (tools/gpu_ab_lib.sh; AB_ARGS extra bench arguments)
 # The per-round one-off wrappers of rounds 2-4 are kept in tools/archive/ (the commands behind
@@ -31,7 +32,7 @@ if [ "${SMOKE:-1}" = 1 ]; then
   tail -1 $out/smoke.log
 fi
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 900 python -u bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $out/bench.json 2> $out/bench.err || exit $?
+  timeout -k 10 900 python -u bench.py --gpus 1 --steps 20 --warmup 5 --full "$@" > $out/bench.json 2> $out/bench.err || exit $?
   python -c "
 import json,sys; d=json.load(open('$out/bench.json'))
 print('headline', '%.4g'%d['value'], 'frac', '%.3f'%d['roofline']['frac'], 'kernel_ms', '%.3f'%d['roofline']['kernel_avg_ms'], 'ess/s', '%.3g'%d['ess_per_s'])
@@ -45,5 +46,5 @@ if [ -n "${PMC:-}" ]; then
   TAG=$name KERNELS="$PMC" BENCH_ARGS="${PMC_ARGS:-}" bash tools/gpu_pmc_traffic.sh || exit $?
 fi
 if [ -n "${AB:-}" ]; then
-  LIBS="$AB" BENCH_ARGS="${AB_ARGS:-}" bash tools/gpu_ab_lib.sh 2>&1 | tee $out/ab.txt
+  OUT=$out LIBS="$AB" BENCH_ARGS="${AB_ARGS:-}" bash tools/gpu_ab_lib.sh 2>&1 | tee $out/ab.txt
 fi

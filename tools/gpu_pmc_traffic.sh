@@ -1,7 +1,7 @@
 #!/bin/bash
 # PMC HBM traffic (FETCH_SIZE and WRITE_SIZE, separate passes) + one SQ pass of a bench.py command,
 # averaged per dispatch for each kernel whose name contains one of KERNELS.
-#   TAG=hyper KERNELS="k_hyper_mh k_bdraw_tiled" BENCH_ARGS="--pta curn_plred ..." bash tools/gpu_pmc_traffic.sh
+#   TAG=hyper KERNELS="k_hyper_mh k_bdraw_tiled" BENCH_ARGS="--full --pta curn_plred ..." bash tools/gpu_pmc_traffic.sh
 set -u
 R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/pmc_${TAG:-x}

@@ -1,14 +1,15 @@
 #!/bin/bash
-# rocprofv3 kernel trace + stats of the driver's bench command (no CPU baseline), and the
+# rocprofv3 kernel trace + stats of the whole bench (--full, no CPU baseline), and the
 # per-launch durations of the dominant kernels.  bash tools/gpu_prof_trace.sh <outdir> [bench args]
 set -u
 out=$GRAFT_REPO_ROOT/gpurun_out/$1
 shift
 mkdir -p $out
 export OPENBLAS_NUM_THREADS=1
+bench=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $out/prof -o run --output-format csv \
-   -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5 "$@" > $out/bench_prof.json 2> $out/prof.err; rc=$?
+   -- python3 $bench --full --no-cpu-baseline --steps 20 --warmup 5 "$@" > $out/bench_prof.json 2> $out/prof.err; rc=$?
 echo "rocprof rc=$rc"
 [ $rc -eq 0 ] || { tail -5 $out/prof.err; exit $rc; }
 cd $GRAFT_REPO_ROOT
