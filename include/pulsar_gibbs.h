@@ -89,9 +89,11 @@ enum {
                          of 16 chains, each trio of waves running a 13th..16th chain in thirds of
                          the sweeps (every wave draws 4/3 chains: n_psr x n_chain = 4096 fills the
                          3072 wave slots of 3 waves/SIMD in one round); 2 = 4-wave workgroups,
-                         one chain per wave; 3 = two chains per wave (NF = 60 tile variant with
-                         device Philox, even chain counts; else as 0), both chains' draws sharing
-                         the diagonal-tile eliminations at 2 waves/SIMD.  gs_bdraw_tiled
+                         one chain per wave; 3 = two chains per wave, both chains' draws sharing
+                         the diagonal-tile eliminations at 2 waves/SIMD (NF = 60 tile variant
+                         with at most 16 fixed-prior columns, device Philox, an even chain count;
+                         where one of these does not hold the launch runs as 2, the 4-wave
+                         shape -- not as 0: the cost model is not consulted).  gs_bdraw_tiled
                          follows it too (3: two chains per wave where NF = 60, no lnL output is
                          attached and the chain count is even; otherwise one chain per wave).
                          The 12-wave shape is used only when its LDS (model

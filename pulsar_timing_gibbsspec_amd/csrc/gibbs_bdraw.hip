@@ -19,6 +19,7 @@
 // the draw law is identical (b ~ N(Sigma^-1 d, Sigma^-1)); with injected normals
 // rotated by the oracle (z' = L^T U S^-1/2 z) the samples coincide.
 #include <cmath>
+#include <type_traits>
 
 #include "gibbs_common.h"
 #include "gibbs_internal.h"
@@ -231,15 +232,11 @@ __device__ __forceinline__ int bdraw_sys(const ModelT& M, int NMX, int nM, int l
 
 // Copy a pulsar's model block into LDS (whole workgroup), 16 bytes per lane and access: model
 // blocks are a 16-byte multiple of doubles (model_stride_doubles) at 16-byte aligned offsets.
-// GS_STAGE_GLDS: by LDS-DMA (global_load_lds_dwordx4: no VGPR round trip, no ds_write), each
-// wave-instruction filling 1 KB of the block lane-linearly.
-#ifndef GS_STAGE_GLDS
-#define GS_STAGE_GLDS 1
-#endif
+// By LDS-DMA (global_load_lds_dwordx4: no VGPR round trip, no ds_write), each wave-instruction
+// filling 1 KB of the block lane-linearly.
 typedef __attribute__((address_space(3))) void* gs_lds_vptr;
 __device__ __forceinline__ void stage_model(double* lds, const double* g, int64_t n) {
   const int n2 = (int)(n >> 1);
-#if GS_STAGE_GLDS
   const int wave = gs_wave_id(), lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   for (int base = wave * 64; base < n2; base += nw * 64) {
     if (base + lane < n2)
@@ -247,12 +244,6 @@ __device__ __forceinline__ void stage_model(double* lds, const double* g, int64_
                                        0);
   }
   gs_wait_dma();
-#else
-  const double2* __restrict__ g2 = reinterpret_cast<const double2*>(g);
-  double2* l2 = reinterpret_cast<double2*>(lds);
-#pragma unroll 4
-  for (int i = threadIdx.x; i < n2; i += blockDim.x) l2[i] = g2[i];
-#endif
   __syncthreads();
 }
 
@@ -260,9 +251,6 @@ __device__ __forceinline__ void stage_model(double* lds, const double* g, int64_
 // gibbs_internal.h model_tiled_*), built in LDS once per launch from the row-major block in
 // global memory (L2): one double per thread and step, amortised over the launch's sweeps.
 // Values are copied (or negated, G) exactly, so the draws are bit-identical to the row-major path.
-#ifndef GS_SWEEP_TILED
-#define GS_SWEEP_TILED 1
-#endif
 // NMX: the batch's fixed-column count (the row-major block's strides); the LDS layout is the
 // pulsar's own, model_tiled_layout(NMX, nM).
 __device__ void stage_model_tiled(double* __restrict__ L, const double* __restrict__ g, int NF, int NMX, int nM) {
@@ -370,20 +358,6 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_bdraw_wide(BdrawArgs A) {
 #ifndef GS_BDRAW_LOOP
 #define GS_BDRAW_LOOP 4
 #endif
-// Shared model converted to the register-tile layout by each workgroup from global memory
-// (stage_model_tiled) -- measured slower in k_bdraw (0.873 ms at loop 1, 0.631-0.661 at loop 4/8):
-// unlike the fused sweep, one launch draws too few systems per workgroup to amortise the conversion.
-#ifndef GS_BDRAW_TILED
-#define GS_BDRAW_TILED 0
-#endif
-// k_bdraw_tiled's persistent ranges in XCD-major order (1) or in workgroup order (0).  Measured on
-// MI355X (r05b, interleaved A/B, 2048 chains x 45 pulsars): XCD-major was SLOWER -- CURN 4.01e6 vs
-// 4.11-4.12e6 chain-it/s, curn_plred 1.75e6 vs 1.78e6 -- although it fetches each pulsar's block
-// into one or two XCDs' L2 instead of eight: the draw is issue bound, and a contiguous run of
-// pulsars per XCD loads the XCDs unevenly (the per-pulsar cost varies with the timing model).  Off.
-#ifndef GS_BDRAW_XCD
-#define GS_BDRAW_XCD 0
-#endif
 // lnl[sys] of k_lnlike_marg from the two factorisation terms (gs_ctx_set_bdraw_lnl)
 __device__ __forceinline__ void bdraw_lnl_store(const BdrawArgs& A, int p, int64_t sys, int NF, int lane, double phinv,
                                                 int fail, double yy, double lp) {
@@ -472,26 +446,14 @@ __global__ __launch_bounds__(64 * WPB, GS_MINW(BC, NFC, NTC)) void k_bdraw(Bdraw
   const int nM = __builtin_amdgcn_readfirstlane(A.nm[p]);  // uniform: SGPR
   const int fi = lane < NF ? A.fidx[p * NF + lane] : 0;
   const int mi = lane < nM ? A.midx[p * A.NMX + lane] : 0;
-  constexpr bool TL = GS_BDRAW_TILED && (BC == GS_BCAST_TILE || NFC == 0);
-  using ModelT = typename std::conditional<TL, ModelTiled, ModelLds>::type;
-  ModelT M;
-  int64_t mlds;
-  int NMXe = A.NMX;
-  if constexpr (TL) {
-    stage_model_tiled(lds, A.model + (int64_t)p * A.mstride, NF, A.NMX, nM);
-    mlds = model_tiled_doubles(NF, A.NMX);
-    M = model_tiled_view_psr<false>(lds, NF, A.NMX, nM, NMXe);
-  } else {
-    stage_model(lds, A.model + (int64_t)p * A.mstride, A.mstride);
-    mlds = A.mstride;
-    M = model_view(lds, NF, A.NMX);
-  }
-  double* scr = lds + mlds + wave * GS_SCR_DOUBLES(BC, NF);
+  stage_model(lds, A.model + (int64_t)p * A.mstride, A.mstride);
+  const ModelLds M = model_view(lds, NF, A.NMX);
+  double* scr = lds + A.mstride + wave * GS_SCR_DOUBLES(BC, NF);
 #pragma unroll 1
   for (int r = 0; r < GS_BDRAW_LOOP; ++r) {
     const int c = (g0 + r) * WPB + wave;
     if (c >= A.n_chain) break;
-    bdraw_item<NFC, NTC, BC>(A, M, p, c, NF, nM, fi, mi, scr, lane, NMXe);
+    bdraw_item<NFC, NTC, BC>(A, M, p, c, NF, nM, fi, mi, scr, lane);
   }
 }
 
@@ -519,11 +481,7 @@ __global__ __launch_bounds__(64 * WPB, GS_MINW(GS_BCAST_TILE, NFC, NTC)) void k_
     // (pulsar, chain group) items [w n / G, (w + 1) n / G) in pulsar-major order: every workgroup
     // draws the same number of groups, restaging the model only where its range crosses a pulsar
     const int64_t n_items = (int64_t)A.n_psr * nb;
-    // GS_BDRAW_XCD (off): XCD-major ranges -- workgroups are dealt round-robin over the 8 XCDs
-    // (blocks b and b + 8 share one, MI355X_MICROARCH.md), so the workgroups of one XCD would take
-    // one contiguous run of items
-    int64_t w = blockIdx.x;
-    if (GS_BDRAW_XCD && (A.persist & 7) == 0) w = (w & 7) * (A.persist >> 3) + (w >> 3);
+    const int64_t w = blockIdx.x;
     const int64_t lo = w * n_items / A.persist, hi = (w + 1) * n_items / A.persist;
     int cur = -1, nM = 0, fi = 0, mi = 0, NMXe = A.NMX;
     ModelTiled M;
@@ -914,20 +872,51 @@ __global__ __launch_bounds__(64 * GS_HY_W, GS_HY_W == 1 ? 2 : 3) void k_hyper_mh
 }
 
 // ------------------------------------------------------------ fused sweep
-// GS_RNG_MERGE (off): one Philox block per lane per sweep for the rho uniforms and the normals.
-// Measured on MI355X (r05d/r05e, interleaved A/B, 4096 chains, 300 launches): 2.078-2.086 ms per
-// launch merged vs 2.042-2.049 with the two blocks -- the crossbar redistribution and the pair kept
-// for Box-Muller raise the 12-wave kernel's spills 6 -> 19-26 VGPRs, which costs more than the 2.0 %
-// the rho uniforms' Philox pass takes (profiles/r05b).
-#ifndef GS_RNG_MERGE
-#define GS_RNG_MERGE 0
+// The analytic rho|b law of one frequency (pulsar_gibbs.py:208-216, 236) for the fused sweeps: from
+// tau = (b_sin^2 + b_cos^2) / 2 and the uniform U, xnew = 0.5 log10 rho and phinv = 1 / rho; both 0 on a
+// lane that is not `act`.  irhomin / irhomax: the reciprocals of the prior bounds.  Called by the whole
+// wave (the ballot).  k_rho_analytic keeps the exact-libm law.
+struct RhoDraw {
+  double xnew, phinv;
+};
+__device__ __forceinline__ RhoDraw rho_given_b(double tau, double U, double rhomin, double rhomax, double irhomin,
+                                               double irhomax, bool act) {
+#if GS_FAST_MATH
+  // the reference's expressions with its divisions by the prior bounds as products with
+  // their reciprocals, tau / den and den / tau by v_rcp_f64 + two Newton steps, and
+  // the short log (gibbs_common.h): ~2 ulp per value, ~150 fewer VALU per draw
+  const double t1 = tau * irhomax;
+  const double arg = t1 - tau * irhomin;
+#else
+  const double t1 = tau / rhomax;
+  const double arg = t1 - (tau / rhomin);
 #endif
-#ifndef GS_RHO_EXP
-#define GS_RHO_EXP 0
+  // 1 - exp(arg) rounds to exactly 1 for arg < -37.5: skip the exp when every
+  // lane is there (the usual case, tau >> rhomin)
+  double hi = 1.0;
+  if (__ballot(act && !(arg < -40.0))) hi = 1 - exp(arg);
+  const double eta = 0.0 + hi * U;
+#if GS_FAST_MATH
+  const double den = t1 - gs_log_pos(1 - eta);
+  const double rho = tau * rcp_nr2(den);
+  const double xnew = act ? gs_log_pos(rho) * 0x1.bcb7b1526e50ep-3 : 0.0;  // 0.5 log10 rho
+  // phiinv = 1/rho = den / tau
+  const double phinv = act ? den * rcp_nr2(tau) : 0.0;
+#else
+  const double den = t1 - log(1 - eta);
+  const double rho = tau / den;
+  const double xnew = act ? 0.5 * log10(rho) : 0.0;
+  // phiinv of the new rho: 1/rho (rcp + two Newton steps) instead of the
+  // reference's 1/10**(2 x) round trip through log10 (equal to a few ulp)
+  const double phinv = act ? rcp_nr2(rho) : 0.0;
 #endif
+  return {xnew, phinv};
+}
+
 // FX: the tiled model block's fixed-prior part in tiles (nm <= 16, k_sweep_freespec) or row-major
 // (k_sweep_freespec_rm): a compile-time choice, so each kernel carries only its own fixed-block
-// code (both in one kernel cost the headline 7 more spilled VGPRs, +1.2 %, r03j).
+// code (both in one kernel cost the headline 7 more spilled VGPRs, +1.2 %, r03j).  Read by the tile
+// variant only: the lane-row variants have no k_sweep_freespec_rm.
 template <int NFC, int NTC, int WPB, int BC, bool FX>
 __device__ __forceinline__ void sweep_freespec_body(const SweepArgs& A) {
   extern __shared__ double lds[];
@@ -936,7 +925,7 @@ __device__ __forceinline__ void sweep_freespec_body(const SweepArgs& A) {
   const int wave = gs_wave_id(), lane = threadIdx.x & 63;
   // tile variant: the model block in the register-tile layout (stage_model_tiled); the lane-row
   // broadcast variants read the row-major block
-  constexpr bool TL = GS_SWEEP_TILED && (BC == GS_BCAST_TILE || NFC == 0);
+  constexpr bool TL = BC == GS_BCAST_TILE || NFC == 0;
   // BAL (12-wave workgroups = 3 waves on each SIMD of a CU, tile variant): 16 chains per
   // workgroup, waves 0..11 own chains 0..11 and each trio (waves 3e, 3e+1, 3e+2) runs chain 12 + e
   // in thirds of the sweeps, handed from wave to wave through LDS -- every wave draws 4/3 chains,
@@ -986,10 +975,6 @@ __device__ __forceinline__ void sweep_freespec_body(const SweepArgs& A) {
   int* hflag =
       reinterpret_cast<int*>(lds + mlds + WPB * (GS_SCR_DOUBLES(BC, NF) + 128 + 256) + NTRIO * 256) + wave / 3;
   GS_PH_INIT(scr)
-#ifdef GS_STATIC_PRIO
-  // A/B knob: half of the workgroups (one of the two co-resident waves of a SIMD) at priority 1
-  if (blockIdx.x & 1) __builtin_amdgcn_s_setprio(1);
-#endif
 
   const double rhomin = A.rhomin, rhomax = A.rhomax;
   const double irhomin = 1.0 / rhomin, irhomax = 1.0 / rhomax;
@@ -1059,15 +1044,6 @@ __device__ __forceinline__ void sweep_freespec_body(const SweepArgs& A) {
     const int64_t brow0 = A.brec_nc == 0 ? sys : (int64_t)p * A.brec_nc + c;
     double* bFp = (brec && act) ? A.b_rec + sw_a * br_step + brow0 * A.ldb + fi : nullptr;
     double* bMp = (brec && actm) ? A.b_rec + sw_a * br_step + brow0 * A.ldb + mi : nullptr;
-  // Merged RNG (production draws: nothing injected): ONE Philox block per lane per sweep feeds both
-  // the rho|b uniforms and the b|rho normals.  Lane l < npair turns its two 53-bit uniforms into the
-  // Box-Muller pair (normals 2l, 2l+1 of [z_F | z_M]); lane npair + j lends its two uniforms to
-  // frequencies 2j, 2j+1 of the rho draw; the values reach their consumer lanes through the LDS
-  // crossbar (ds_bpermute, no VALU).  One Philox pass per sweep instead of two (the separate rho
-  // uniforms cost 2.0 % of the headline launch, profiles/r05b); falls back to the two-block scheme
-  // when the lanes do not suffice (NF + nM + NF / 2 > 128).
-  const int npair = (NF + nM + 1) >> 1;
-  const bool mrg = GS_RNG_MERGE && !A.u_inj && !A.z_inj && npair + ((NFR + 1) >> 1) <= 64;
 #pragma unroll 1
   for (int sw = sw_a; sw < sw_b; ++sw) {
     const long long ii = A.it0 + sw;
@@ -1098,62 +1074,13 @@ __device__ __forceinline__ void sweep_freespec_body(const SweepArgs& A) {
         double U;
         if (A.u_inj) {
           U = act ? A.u_inj[rec * NFR + kf] : 0.5;
-        } else if (mrg) {
-          double mu1, mu2;
-          gs_uniform2(gs_counter(lane, ii, gchain, p + A.psr_base, GS_EV_B), A.key, mu1, mu2);
-          const int src = npair + (kf >> 1);
-          const double ua = gtile::bcast_lane_bp(mu1, src), ub = gtile::bcast_lane_bp(mu2, src);
-          U = (kf & 1) ? ub : ua;
-          // the pair waits for Box-Muller in the wave's save slot (free until the draw), not in
-          // 4 VGPRs across the rho step (26 spilled VGPRs that way)
-          bsave[lane] = mu1;
-          bsave[64 + lane] = mu2;
         } else {
           double u2;
-#ifdef GS_PROBE_NO_RHO_PHILOX  // cost attribution only (wrong draws): the rho uniform without Philox
-          U = 0.25 + 0.5 * __builtin_amdgcn_fract(tau * 1e3);
-          (void)u2;
-#else
           gs_uniform2(gs_counter(kf, ii, gchain, p + A.psr_base, GS_EV_RHO), A.key, U, u2);
-#endif
         }
-#if GS_FAST_MATH
-        // the reference's expressions with its divisions by the prior bounds as products with
-        // their reciprocals, tau / den and den / tau by v_rcp_f64 + two Newton steps, and
-        // the short log (gibbs_common.h): ~2 ulp per value, ~150 fewer VALU per draw
-        const double t1 = tau * irhomax;
-        const double arg = t1 - tau * irhomin;
-#else
-        const double t1 = tau / rhomax;
-        const double arg = t1 - (tau / rhomin);
-#endif
-        // 1 - exp(arg) rounds to exactly 1 for arg < -37.5: skip the exp when every
-        // lane is there (the usual case, tau >> rhomin)
-        double hi = 1.0;
-#if GS_FAST_MATH && GS_RHO_EXP
-        if (__ballot(act && !(arg < -40.0))) hi = 1 - gs_exp_neg(arg);  // arg <= 0 (rhomin < rhomax)
-#else
-        if (__ballot(act && !(arg < -40.0))) hi = 1 - exp(arg);
-#endif
-        const double eta = 0.0 + hi * U;
-#if GS_FAST_MATH
-#ifdef GS_PROBE_NO_RHO_LOG  // cost attribution only (wrong draws)
-        const double den = t1 + eta;
-#else
-        const double den = t1 - gs_log_pos(1 - eta);
-#endif
-        const double rho = tau * rcp_nr2(den);
-        const double xnew = act ? gs_log_pos(rho) * 0x1.bcb7b1526e50ep-3 : 0.0;  // 0.5 log10 rho
-        // phiinv = 1/rho = den / tau
-        phinv = act ? den * rcp_nr2(tau) : 0.0;
-#else
-        const double den = t1 - log(1 - eta);
-        const double rho = tau / den;
-        const double xnew = act ? 0.5 * log10(rho) : 0.0;
-        // phiinv of the new rho: 1/rho (rcp + two Newton steps) instead of the
-        // reference's 1/10**(2 x) round trip through log10 (equal to a few ulp)
-        phinv = act ? rcp_nr2(rho) : 0.0;
-#endif
+        const RhoDraw rd = rho_given_b(tau, U, rhomin, rhomax, irhomin, irhomax, act);
+        const double xnew = rd.xnew;
+        phinv = rd.phinv;
         // gate: all(xnew != x_old[-1])  (pulsar_gibbs.py:697)
         const double xlast = rdlane(x, NF - 1);
         const bool same = act && (xnew == xlast);
@@ -1171,25 +1098,7 @@ __device__ __forceinline__ void sweep_freespec_body(const SweepArgs& A) {
         zF = act ? zinj[zrow * A.ldb + fi] : 0.0;
         zM = actm ? zinj[zrow * A.ldb + mi] : 0.0;
       } else {
-#ifdef GS_PROBE_NO_NORMALS  // cost attribution only (wrong draws): no Philox + Box-Muller pass
-        zF = __builtin_amdgcn_fract(x * 7.0) - 0.5;
-        zM = __builtin_amdgcn_fract(x * 3.0) - 0.5;
-#else
-        if (mrg && pass == 1) {
-          // normal j of [z_F | z_M] is component j & 1 of lane j >> 1's pair
-          double n1, n2;
-          gtile::lds_fence();
-          gs_box_muller(bsave[lane], bsave[64 + lane], n1, n2);
-          gtile::lds_fence();
-          const int sf = lane >> 1, sm = (NF + lane) >> 1;
-          const double f1 = gtile::bcast_lane_bp(n1, sf), f2 = gtile::bcast_lane_bp(n2, sf);
-          const double m1 = gtile::bcast_lane_bp(n1, sm), m2 = gtile::bcast_lane_bp(n2, sm);
-          zF = (lane & 1) ? f2 : f1;
-          zM = ((NF + lane) & 1) ? m2 : m1;
-        } else {
-          gs_normal2(gs_counter(lane, ii, gchain, p + A.psr_base, ev), A.key, zF, zM);
-        }
-#endif
+        gs_normal2(gs_counter(lane, ii, gchain, p + A.psr_base, ev), A.key, zF, zM);
       }
       if (pass == 0) phinv = act ? 1.0 / pow(10.0, 2.0 * x) : 0.0;  // first draw from xs
       GS_PH(7)
@@ -1249,6 +1158,7 @@ __global__ __launch_bounds__(64 * WPB, GS_MINW(BC, NFC, NTC)) void k_sweep_frees
 // bit: the Philox counters are per chain, a chain whose gate is shut has its (computed) draw discarded
 // exactly where the one-chain kernel skips it, and a failed factorisation keeps that chain's b.
 // 2 waves per SIMD (both chains' tiles: ~200 VGPRs): 4096 chains are 2048 waves, one round.
+// per wave: 2 scratches, b save, z_M, x park
 constexpr int GS_PAIR_SCR = 2 * gs_tile_scr(60) + 256 + 128 + 128;
 // GS_PAIR_WPB: waves (chain pairs) per workgroup
 #ifndef GS_PAIR_WPB
@@ -1260,10 +1170,6 @@ constexpr int GS_PAIR_SCR = 2 * gs_tile_scr(60) + 256 + 128 + 128;
 #ifndef GS_PAIR_RHO_PRIO
 #define GS_PAIR_RHO_PRIO 1
 #endif
-// GS_PAIR_RHO_MERGE: both chains' rho steps in one pass over the wave (30 frequencies each)
-#ifndef GS_PAIR_RHO_MERGE
-#define GS_PAIR_RHO_MERGE 1
-#endif  // per wave: 2 scratches, b save, z_M, x park
 
 template <int WPB>
 __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
@@ -1332,7 +1238,6 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
       bool draw[2] = {true, true};
       if (pass == 1) {
         if constexpr (GS_PAIR_RHO_PRIO > 0) __builtin_amdgcn_s_setprio(GS_PAIR_RHO_PRIO);
-#if GS_PAIR_RHO_MERGE
         {
           // rho|b analytic (pulsar_gibbs.py:208-216, 236), as sweep_freespec_body, for both chains in
           // one pass: lane 32 h + k computes frequency k of chain h (the one-chain layout has each
@@ -1351,33 +1256,10 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
           const double tau = h ? tb : ta;
           double U, u2;
           gs_uniform2(gs_counter(k, ii, h ? gchain[1] : gchain[0], p + A.psr_base, GS_EV_RHO), A.key, U, u2);
-#if GS_FAST_MATH
-          const double t1 = tau * irhomax;
-          const double arg = t1 - tau * irhomin;
-#else
-          const double t1 = tau / A.rhomax;
-          const double arg = t1 - (tau / A.rhomin);
-#endif
-          // (1 - exp(arg) is exactly 1 where the skip applies, so one ballot over both chains draws
-          // the same values as a ballot per chain)
-          double hi = 1.0;
-#if GS_FAST_MATH && GS_RHO_EXP
-          if (__ballot(am && !(arg < -40.0))) hi = 1 - gs_exp_neg(arg);
-#else
-          if (__ballot(am && !(arg < -40.0))) hi = 1 - exp(arg);
-#endif
-          const double eta = 0.0 + hi * U;
-#if GS_FAST_MATH
-          const double den = t1 - gs_log_pos(1 - eta);
-          const double rho = tau * rcp_nr2(den);
-          const double xnew = am ? gs_log_pos(rho) * 0x1.bcb7b1526e50ep-3 : 0.0;
-          const double phm = am ? den * rcp_nr2(tau) : 0.0;
-#else
-          const double den = t1 - log(1 - eta);
-          const double rho = tau / den;
-          const double xnew = am ? 0.5 * log10(rho) : 0.0;
-          const double phm = am ? rcp_nr2(rho) : 0.0;
-#endif
+          // (1 - exp(arg) is exactly 1 where the law skips the exp, so its one ballot over both chains
+          // draws the same values as a ballot per chain)
+          const RhoDraw rd = rho_given_b(tau, U, A.rhomin, A.rhomax, irhomin, irhomax, am);
+          const double xnew = rd.xnew, phm = rd.phinv;
           // gate: all(xnew != x_old[-1])  (pulsar_gibbs.py:697), per chain
           const double xl0 = rdlane(x[0], NF - 1), xl1 = rdlane(x[1], NF - 1);
           const unsigned long long same = __ballot(am && (xnew == (h ? xl1 : xl0)));
@@ -1392,46 +1274,6 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
             phinv[ch] = act ? pv : 0.0;
           }
         }
-#else
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch) {
-          // rho|b analytic (pulsar_gibbs.py:208-216, 236), as sweep_freespec_body
-          const double partner = __shfl_xor(bF[ch], 1);
-          const double be = (lane & 1) ? partner : bF[ch], bo = (lane & 1) ? bF[ch] : partner;
-          const double tau = gs_add_rn(gs_mul_rn(be, be), gs_mul_rn(bo, bo)) / 2;
-          double U, u2;
-          gs_uniform2(gs_counter(kf, ii, gchain[ch], p + A.psr_base, GS_EV_RHO), A.key, U, u2);
-#if GS_FAST_MATH
-          const double t1 = tau * irhomax;
-          const double arg = t1 - tau * irhomin;
-#else
-          const double t1 = tau / A.rhomax;
-          const double arg = t1 - (tau / A.rhomin);
-#endif
-          double hi = 1.0;
-#if GS_FAST_MATH && GS_RHO_EXP
-          if (__ballot(act && !(arg < -40.0))) hi = 1 - gs_exp_neg(arg);
-#else
-          if (__ballot(act && !(arg < -40.0))) hi = 1 - exp(arg);
-#endif
-          const double eta = 0.0 + hi * U;
-#if GS_FAST_MATH
-          const double den = t1 - gs_log_pos(1 - eta);
-          const double rho = tau * rcp_nr2(den);
-          const double xnew = act ? gs_log_pos(rho) * 0x1.bcb7b1526e50ep-3 : 0.0;
-          phinv[ch] = act ? den * rcp_nr2(tau) : 0.0;
-#else
-          const double den = t1 - log(1 - eta);
-          const double rho = tau / den;
-          const double xnew = act ? 0.5 * log10(rho) : 0.0;
-          phinv[ch] = act ? rcp_nr2(rho) : 0.0;
-#endif
-          // gate: all(xnew != x_old[-1])  (pulsar_gibbs.py:697)
-          const double xlast = rdlane(x[ch], NF - 1);
-          draw[ch] = __ballot(act && (xnew == xlast)) == 0ull;
-          x[ch] = xnew;
-        }
-#endif
         if constexpr (GS_PAIR_RHO_PRIO > 0) __builtin_amdgcn_s_setprio(GS_BASE_PRIO);
         if (!draw[0] && !draw[1]) break;
         ev = GS_EV_B;
@@ -1439,12 +1281,7 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
       double zF[2], zM[2];
 #pragma unroll
       for (int ch = 0; ch < 2; ++ch) {
-#ifdef GS_PROBE_NO_NORMALS  // cost attribution only (wrong draws): no Philox + Box-Muller pass
-        zF[ch] = __builtin_amdgcn_fract(x[ch] * 7.0) - 0.5;
-        zM[ch] = __builtin_amdgcn_fract(x[ch] * 3.0) - 0.5;
-#else
         gs_normal2(gs_counter(lane, ii, gchain[ch], p + A.psr_base, ev), A.key, zF[ch], zM[ch]);
-#endif
         if (pass == 0) phinv[ch] = act ? 1.0 / pow(10.0, 2.0 * x[ch]) : 0.0;  // first draw from xs
         // the previous b waits in the wave's save slot (a failed or shut draw keeps it)
         bsave[128 * ch + lane] = bF[ch];
@@ -1515,56 +1352,86 @@ extern "C" int gs_debug_phase_cycles(unsigned long long* out, int reset) {
 }
 #endif
 
-// Fixed NF in {20, 40, 60}: every broadcast variant; any other even NF <= 64: the tile
-// variant with NF at run time, one instantiation per tile count NT = NF / 16 + 1.
-// dynamic LDS above 64 KB (nm up to 64: model blocks up to 95 KB) needs the kernel attribute
+// Launch `kernel`; dynamic LDS above 64 KB (nm up to 64: model blocks up to 95 KB) needs the kernel
+// attribute first.
 template <typename K>
 int set_lds(K kernel, size_t lds) {
   return hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
          hipSuccess;
 }
-#define GS_LAUNCH(KERNEL, NFC, NTC, BC, ARGS)                                              \
-  if (lds > 65536 && set_lds(KERNEL<NFC, NTC, WPB, BC>, lds)) return 2;                     \
-  hipLaunchKernelGGL((KERNEL<NFC, NTC, WPB, BC>), grid, dim3(64 * WPB), lds, s, ARGS);     \
+template <typename K, typename ArgsT>
+int launch_lds(K kernel, dim3 grid, int threads, size_t lds, hipStream_t s, const ArgsT& a) {
+  if (lds > 65536 && set_lds(kernel, lds)) return 2;
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, s, a);
   return 0;
-#define GS_NF_CASES(KERNEL, ARGS)                                                       \
-  switch (NF * 4 + bc) {                                                                \
-    case 80: GS_LAUNCH(KERNEL, 20, 0, 0, ARGS)                                          \
-    case 81: GS_LAUNCH(KERNEL, 20, 0, 1, ARGS)                                          \
-    case 82: GS_LAUNCH(KERNEL, 20, 0, 2, ARGS)                                          \
-    case 83: GS_LAUNCH(KERNEL, 20, 0, 3, ARGS)                                          \
-    case 160: GS_LAUNCH(KERNEL, 40, 0, 0, ARGS)                                         \
-    case 161: GS_LAUNCH(KERNEL, 40, 0, 1, ARGS)                                         \
-    case 162: GS_LAUNCH(KERNEL, 40, 0, 2, ARGS)                                         \
-    case 163: GS_LAUNCH(KERNEL, 40, 0, 3, ARGS)                                         \
-    case 240: GS_LAUNCH(KERNEL, 60, 0, 0, ARGS)                                         \
-    case 241: GS_LAUNCH(KERNEL, 60, 0, 1, ARGS)                                         \
-    case 242: GS_LAUNCH(KERNEL, 60, 0, 2, ARGS)                                         \
-    case 243: GS_LAUNCH(KERNEL, 60, 0, 3, ARGS)                                         \
-    default: break;                                                                     \
-  }                                                                                     \
-  if (NF <= 0 || NF > 64 || (NF & 1)) return 1;                                         \
-  switch (NF / 16 + 1) {                                                                \
-    case 1: GS_LAUNCH(KERNEL, 0, 1, 3, ARGS)                                            \
-    case 2: GS_LAUNCH(KERNEL, 0, 2, 3, ARGS)                                            \
-    case 3: GS_LAUNCH(KERNEL, 0, 3, 3, ARGS)                                            \
-    case 4: GS_LAUNCH(KERNEL, 0, 4, 3, ARGS)                                            \
-    default: GS_LAUNCH(KERNEL, 0, 5, 3, ARGS)                                           \
+}
+
+// The instantiation of a b-draw kernel for NF: NF in {20, 40, 60} at compile time (NFC = NF, NTC = 0);
+// any other even NF <= 64 at run time, one instantiation per tile count (NFC = 0, NTC = NF / 16 + 1; the
+// tile variant only).  f(integral_constant NFC, integral_constant NTC) launches it and returns the
+// launch's status; 1 for an NF that no kernel takes.
+template <int N>
+using gs_int = std::integral_constant<int, N>;
+template <typename F>
+int dispatch_nf(int NF, F&& f) {
+  switch (NF) {
+    case 20: return f(gs_int<20>(), gs_int<0>());
+    case 40: return f(gs_int<40>(), gs_int<0>());
+    case 60: return f(gs_int<60>(), gs_int<0>());
+    default: break;
+  }
+  if (NF <= 0 || NF > 64 || (NF & 1)) return 1;
+  switch (NF / 16 + 1) {
+    case 1: return f(gs_int<0>(), gs_int<1>());
+    case 2: return f(gs_int<0>(), gs_int<2>());
+    case 3: return f(gs_int<0>(), gs_int<3>());
+    case 4: return f(gs_int<0>(), gs_int<4>());
+    default: return f(gs_int<0>(), gs_int<5>());
+  }
+}
+
+// The lane-row broadcast variants (GS_OPT_BCAST 0 / 1 / 2) exist for the fixed NF only.
+#define GS_LANE_ROW_CASES(KERNEL)                                                                     \
+  if constexpr (NFC > 0) {                                                                            \
+    switch (bc) {                                                                                     \
+      case 0: return launch_lds(KERNEL<NFC, 0, WPB, 0>, grid, 64 * WPB, lds, s, a);                    \
+      case 1: return launch_lds(KERNEL<NFC, 0, WPB, 1>, grid, 64 * WPB, lds, s, a);                    \
+      case 2: return launch_lds(KERNEL<NFC, 0, WPB, 2>, grid, 64 * WPB, lds, s, a);                    \
+      default: break;                                                                                 \
+    }                                                                                                 \
   }
 
+// The fused sweep's tile variant: the fixed block of the staged model tiled (NMX <= 16) or row-major.
+template <int WPB>
+int dispatch_nf_sweep_tile(int NF, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
+  const bool fx = model_tiled_fix(a.NMX);
+  return dispatch_nf(NF, [&](auto nfc, auto ntc) {
+    constexpr int NFC = decltype(nfc)::value, NTC = decltype(ntc)::value;
+    return fx ? launch_lds(k_sweep_freespec<NFC, NTC, WPB, 3>, grid, 64 * WPB, lds, s, a)
+              : launch_lds(k_sweep_freespec_rm<NFC, NTC, WPB, 3>, grid, 64 * WPB, lds, s, a);
+  });
+}
+// Every variant (the one-chain-per-wave shape).  The lane-row variants read the row-major block, not the
+// tiled one, so k_sweep_freespec serves them whatever NMX.
 template <int WPB>
 int dispatch_nf_sweep(int NF, int bc, dim3 grid, size_t lds, hipStream_t s, const SweepArgs& a) {
-  if (model_tiled_fix(a.NMX)) {
-    GS_NF_CASES(k_sweep_freespec, a)
-  } else {
-    GS_NF_CASES(k_sweep_freespec_rm, a)
-  }
+  if (bc == GS_BCAST_TILE) return dispatch_nf_sweep_tile<WPB>(NF, grid, lds, s, a);
+  return dispatch_nf(NF, [&](auto nfc, auto) {
+    constexpr int NFC = decltype(nfc)::value;
+    GS_LANE_ROW_CASES(k_sweep_freespec)
+    return dispatch_nf_sweep_tile<WPB>(NF, grid, lds, s, a);  // NF at run time: the tile variant
+  });
 }
 
 template <int WPB>
 int dispatch_nf_bdraw(int NF, int bc, dim3 grid, size_t lds, hipStream_t s, const BdrawArgs& a) {
-  GS_NF_CASES(k_bdraw, a)
+  return dispatch_nf(NF, [&](auto nfc, auto ntc) {
+    constexpr int NFC = decltype(nfc)::value, NTC = decltype(ntc)::value;
+    GS_LANE_ROW_CASES(k_bdraw)
+    return launch_lds(k_bdraw<NFC, NTC, WPB, 3>, grid, 64 * WPB, lds, s, a);
+  });
 }
+#undef GS_LANE_ROW_CASES
 
 }  // namespace
 
@@ -1575,27 +1442,10 @@ int launch_lnlike_marg(hipStream_t s, const LnlArgs& a) {
   dim3 grid((unsigned)(a.n_psr * (in_lds ? (nb + GS_BDRAW_LOOP - 1) / GS_BDRAW_LOOP : nb)));
   const size_t lds = ((size_t)(a.model_per_sys || a.model_global ? 0 : a.mstride) + gs_tile_scr(a.NF) * WPB) *
                      sizeof(double);
-  // a shared model block staged in LDS: above 64 KB (e.g. NF = 60 with NMX > 31) the launch needs
-  // the dynamic-LDS attribute, as GS_LAUNCH sets it
-#define GS_LNL_LAUNCH(NFC, NTC)                                                       \
-  if (lds > 65536 && set_lds(k_lnlike_marg<NFC, NTC, WPB>, lds)) return 2;            \
-  hipLaunchKernelGGL((k_lnlike_marg<NFC, NTC, WPB>), grid, dim3(64 * WPB), lds, s, a); \
-  return 0;
-  switch (a.NF) {
-    case 20: GS_LNL_LAUNCH(20, 0)
-    case 40: GS_LNL_LAUNCH(40, 0)
-    case 60: GS_LNL_LAUNCH(60, 0)
-    default: break;
-  }
-  if (a.NF <= 0 || a.NF > 64 || (a.NF & 1)) return 1;
-  switch (a.NF / 16 + 1) {
-    case 1: GS_LNL_LAUNCH(0, 1)
-    case 2: GS_LNL_LAUNCH(0, 2)
-    case 3: GS_LNL_LAUNCH(0, 3)
-    case 4: GS_LNL_LAUNCH(0, 4)
-    default: GS_LNL_LAUNCH(0, 5)
-  }
-#undef GS_LNL_LAUNCH
+  // (a shared model block staged in LDS is above 64 KB at e.g. NF = 60 with NMX > 31)
+  return dispatch_nf(a.NF, [&](auto nfc, auto ntc) {
+    return launch_lds(k_lnlike_marg<decltype(nfc)::value, decltype(ntc)::value, WPB>, grid, 64 * WPB, lds, s, a);
+  });
 }
 
 int launch_hyper_mh(hipStream_t s, const HyperMhArgs& a) {
@@ -1603,25 +1453,9 @@ int launch_hyper_mh(hipStream_t s, const HyperMhArgs& a) {
   // x row, lnL_p, the 64-step proposal table, each wave's tile scratch
   const size_t lds = ((size_t)((a.ldx + a.n_psr + 1) & ~1) + 4 * 64 + GS_HY_W * gs_tile_scr(a.NF)) * sizeof(double);
   dim3 grid((unsigned)a.n_chain);
-#define GS_HY_LAUNCH(NFC, NTC)                                                   \
-  if (lds > 65536 && set_lds(k_hyper_mh<NFC, NTC>, lds)) return 2;               \
-  hipLaunchKernelGGL((k_hyper_mh<NFC, NTC>), grid, dim3(64 * GS_HY_W), lds, s, a); \
-  return 0;
-  switch (a.NF) {
-    case 20: GS_HY_LAUNCH(20, 0)
-    case 40: GS_HY_LAUNCH(40, 0)
-    case 60: GS_HY_LAUNCH(60, 0)
-    default: break;
-  }
-  if (a.NF <= 0 || a.NF > 64 || (a.NF & 1)) return 1;
-  switch (a.NF / 16 + 1) {
-    case 1: GS_HY_LAUNCH(0, 1)
-    case 2: GS_HY_LAUNCH(0, 2)
-    case 3: GS_HY_LAUNCH(0, 3)
-    case 4: GS_HY_LAUNCH(0, 4)
-    default: GS_HY_LAUNCH(0, 5)
-  }
-#undef GS_HY_LAUNCH
+  return dispatch_nf(a.NF, [&](auto nfc, auto ntc) {
+    return launch_lds(k_hyper_mh<decltype(nfc)::value, decltype(ntc)::value>, grid, 64 * GS_HY_W, lds, s, a);
+  });
 }
 
 // Workgroup shape of the tile-variant sweep (GS_OPT_SWEEP_SCHED 0: this cost model).  In units
@@ -1652,15 +1486,22 @@ static size_t device_lds_optin() {
   }
   return (size_t)lim;
 }
-static bool sweep_handoff_wins(const SweepArgs& a) {
-  if (a.sched) return a.sched == 1;
+// rounds R of the launch in the two one-chain shapes: 4-wave workgroups, 12-wave hand-off workgroups
+struct OneChainRounds {
+  double w4, w12;
+};
+static OneChainRounds one_chain_rounds(const SweepArgs& a) {
   const double ncu = device_cus();
   const double q = (double)a.n_psr * a.n_chain / (4.0 * ncu);
   const double k = std::floor(q / 3.0), r = q - 3.0 * k;
   const double g = r <= 0.0 ? 0.0 : r <= 1.0 ? 0.46 * r : r <= 2.0 ? 0.46 + 0.28 * (r - 1.0) : 0.74 + 0.26 * (r - 2.0);
   const double wg = (double)a.n_psr * ((a.n_chain + 15) / 16);
-  const double c12 = std::ceil(wg / ncu) * (4.0 / 3.0);
-  return c12 < 0.97 * (k + g);
+  return {k + g, std::ceil(wg / ncu) * (4.0 / 3.0)};
+}
+static bool sweep_handoff_wins(const SweepArgs& a) {
+  if (a.sched) return a.sched == 1;
+  const OneChainRounds one = one_chain_rounds(a);
+  return one.w12 < 0.97 * one.w4;
 }
 // Two chains per wave (k_sweep_pair) against the one-chain shapes, in the same unit R.  Its waves run
 // 2 per SIMD: a full round (8 waves per CU, 16 chains) takes P = 1.27 R and a last round of at most one
@@ -1670,11 +1511,8 @@ static bool sweep_handoff_wins(const SweepArgs& a) {
 static bool sweep_pair_wins(const SweepArgs& a) {
   if (a.sched) return a.sched == 3;
   const double ncu = device_cus();
-  const double q = (double)a.n_psr * a.n_chain / (4.0 * ncu);
-  const double k = std::floor(q / 3.0), r = q - 3.0 * k;
-  const double g = r <= 0.0 ? 0.0 : r <= 1.0 ? 0.46 * r : r <= 2.0 ? 0.46 + 0.28 * (r - 1.0) : 0.74 + 0.26 * (r - 2.0);
-  const double wg = (double)a.n_psr * ((a.n_chain + 15) / 16);
-  const double one = std::min(k + g, std::ceil(wg / ncu) * (4.0 / 3.0));
+  const OneChainRounds oc = one_chain_rounds(a);
+  const double one = std::min(oc.w4, oc.w12);
   const double w = (double)a.n_psr * (a.n_chain / 2) / (4.0 * ncu);  // pair waves per SIMD
   const double kp = std::floor(w / 2.0), rp = w - 2.0 * kp;
   const double pair = 1.27 * (kp + (rp <= 0.0 ? 0.0 : rp <= 1.0 ? 0.70 : 1.0));
@@ -1682,7 +1520,7 @@ static bool sweep_pair_wins(const SweepArgs& a) {
 }
 int launch_sweep_freespec(hipStream_t s, const SweepArgs& a, int* shape) {
   const bool fixed = a.NF == 20 || a.NF == 40 || a.NF == 60;
-  const bool tiled = GS_SWEEP_TILED && (!fixed || a.bcast == GS_BCAST_TILE);
+  const bool tiled = !fixed || a.bcast == GS_BCAST_TILE;
   const size_t mlds = tiled ? (size_t)model_tiled_doubles(a.NF, a.NMX) : (size_t)a.mstride;
   // two chains per wave (k_sweep_pair): NF = 60 on the tiled block with a tiled fixed part, device
   // Philox (no injected draws), an even chain count
@@ -1707,7 +1545,7 @@ int launch_sweep_freespec(hipStream_t s, const SweepArgs& a, int* shape) {
     const int nb = (a.n_chain + 15) / 16;
     dim3 grid((unsigned)(a.n_psr * nb));
     *shape = 1;
-    return dispatch_nf_sweep<12>(a.NF, a.bcast, grid, lds12, s, a);
+    return dispatch_nf_sweep_tile<12>(a.NF, grid, lds12, s, a);
   }
   const int nb = (a.n_chain + GS_SWEEP_WPB - 1) / GS_SWEEP_WPB;
   dim3 grid((unsigned)(a.n_psr * nb));
@@ -1736,8 +1574,7 @@ int launch_bdraw(hipStream_t s, const BdrawArgs& a) {
   const int nb = (a.n_chain + WPB - 1) / WPB;
   dim3 grid((unsigned)(a.n_psr * (a.model_per_sys ? nb : (nb + GS_BDRAW_LOOP - 1) / GS_BDRAW_LOOP)));
   const bool fixed = a.NF == 20 || a.NF == 40 || a.NF == 60;
-  const bool tiled = GS_BDRAW_TILED && (!fixed || a.bcast == GS_BCAST_TILE);
-  const size_t mlds = a.model_per_sys ? 0 : tiled ? (size_t)model_tiled_doubles(a.NF, a.NMX) : (size_t)a.mstride;
+  const size_t mlds = a.model_per_sys ? 0 : (size_t)a.mstride;
   const size_t lds = (mlds + (fixed ? GS_SCR_DOUBLES(a.bcast, a.NF) : gs_tile_scr(a.NF)) * WPB) *
                      sizeof(double);
   return dispatch_nf_bdraw<WPB>(a.NF, a.bcast, grid, lds, s, a);
@@ -1793,46 +1630,27 @@ int launch_bdraw_tiled(hipStream_t s, const BdrawArgs& a0, int* shape) {
   const int nb = (a.n_chain + WPB - 1) / WPB;
   const int64_t nwg = (int64_t)a.n_psr * ((nb + GS_BDRAW_LOOP - 1) / GS_BDRAW_LOOP);
   const size_t lds = ((size_t)a.mstride + (size_t)gs_tile_scr(a.NF) * WPB) * sizeof(double);
-  const int NF = a.NF;
   static const int persist_env = getenv("GS_BDRAW_PERSIST") ? atoi(getenv("GS_BDRAW_PERSIST")) : 1;
   // persistent shape: one round of resident workgroups when the classic grid needs more than one
-#define GS_TL_K(NFC, NTC, FX, LD)                                                                 \
-  {                                                                                               \
-    auto kern = k_bdraw_tiled<NFC, NTC, WPB, FX, LD>;                                             \
-    if (lds > 65536 && set_lds(kern, lds)) return 2;                                              \
-    int per_cu = 0;                                                                               \
-    if (persist_env && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * WPB, lds) == hipSuccess && \
-        per_cu > 0 && nwg > (int64_t)per_cu * device_cus())                                       \
-      a.persist = per_cu * device_cus();                                                          \
-    dim3 grid((unsigned)(a.persist ? a.persist : nwg));                                           \
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WPB), lds, s, a);                                    \
-    return 0;                                                                                     \
-  }
-#define GS_TL_LAUNCH(NFC, NTC)                 \
-  if (fx) {                                    \
-    if (a.lnl) GS_TL_K(NFC, NTC, true, true)   \
-    GS_TL_K(NFC, NTC, true, false)             \
-  } else {                                     \
-    if (a.lnl) GS_TL_K(NFC, NTC, false, true)  \
-    GS_TL_K(NFC, NTC, false, false)            \
-  }
+  auto launch = [&](auto kern) {
+    if (lds > 65536 && set_lds(kern, lds)) return 2;
+    int per_cu = 0;
+    if (persist_env && hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * WPB, lds) == hipSuccess &&
+        per_cu > 0 && nwg > (int64_t)per_cu * device_cus())
+      a.persist = per_cu * device_cus();
+    dim3 grid((unsigned)(a.persist ? a.persist : nwg));
+    hipLaunchKernelGGL(kern, grid, dim3(64 * WPB), lds, s, a);
+    return 0;
+  };
   const bool fx = model_tiled_fix(a.NMX);
-  switch (NF) {
-    case 20: GS_TL_LAUNCH(20, 0)
-    case 40: GS_TL_LAUNCH(40, 0)
-    case 60: GS_TL_LAUNCH(60, 0)
-    default: break;
-  }
-  if (NF <= 0 || NF > 64 || (NF & 1)) return 1;
-  switch (NF / 16 + 1) {
-    case 1: GS_TL_LAUNCH(0, 1)
-    case 2: GS_TL_LAUNCH(0, 2)
-    case 3: GS_TL_LAUNCH(0, 3)
-    case 4: GS_TL_LAUNCH(0, 4)
-    default: GS_TL_LAUNCH(0, 5)
-  }
-#undef GS_TL_LAUNCH
-#undef GS_TL_K
+  return dispatch_nf(a.NF, [&](auto nfc, auto ntc) {
+    constexpr int NFC = decltype(nfc)::value, NTC = decltype(ntc)::value;
+    if (fx)
+      return a.lnl ? launch(k_bdraw_tiled<NFC, NTC, WPB, true, true>)
+                   : launch(k_bdraw_tiled<NFC, NTC, WPB, true, false>);
+    return a.lnl ? launch(k_bdraw_tiled<NFC, NTC, WPB, false, true>)
+                 : launch(k_bdraw_tiled<NFC, NTC, WPB, false, false>);
+  });
 }
 
 int launch_rho_analytic(hipStream_t s, const RhoArgs& a) {

@@ -34,51 +34,12 @@ __host__ __device__ constexpr int ptk(int k) { return 2 * (k >> 2) + ((k >> 1) &
 
 }  // namespace gpair
 
-// GS_PAIR_SKIP: the paired elimination updates only the registers holding rows it needs (one fmac
-// fewer per step than the row-group granularity of tile_elim1)
-#ifndef GS_PAIR_SKIP
-#define GS_PAIR_SKIP 1
-#endif
-// GS_PAIR_T2: both chains' tile transposes in one LDS round trip (1) or one after the other (0).
-// Measured (r06o, headline): 2.004-2.012 ms per launch against 1.953-1.962 -- the paired form holds
-// both chains' tiles live across the round trip (20 VGPRs spilled instead of 10)
-#ifndef GS_PAIR_T2
-#define GS_PAIR_T2 0
-#endif
 // GS_PAIR_FIX_PRIO: issue priority of the pair draw's fixed block (the one-chain tile core: GS_FIX_PRIO
 // = 0).  Measured on the headline (r06p2, 3 interleaved reps): 1.901-1.907 ms per launch at 1 against
 // 1.910-1.922 at 0; the MFMA updates at 1 (1.908-1.913) and the elimination at 1 (1.936-1.943) not
 #ifndef GS_PAIR_FIX_PRIO
 #define GS_PAIR_FIX_PRIO 1
 #endif
-// GS_PAIR_LOOKAHEAD: step K's trailing updates other than the next diagonal tile are issued inside the
-// next diagonal elimination, one tile-op per pivot step (each tile still sees its updates in K order, so
-// the draws are unchanged bit for bit; at NT = 4 at most 10 tile-ops wait, fewer than the 16 steps).
-// Measured on the headline (r06la, 3 interleaved reps): 1.912-1.920 ms per launch against 1.916-1.925
-#ifndef GS_PAIR_LOOKAHEAD
-#define GS_PAIR_LOOKAHEAD 1
-#endif
-// GS_PAIR_SOLVE_ILV: both chains' solves and fixed blocks interleaved (1) or one after the other (0)
-#ifndef GS_PAIR_SOLVE_ILV
-#define GS_PAIR_SOLVE_ILV 1
-#endif
-
-// gtile::transpose of two chains' tiles through their own LDS staging tiles, one round trip for both
-__device__ __forceinline__ void transpose2(gs_d4& t0, gs_d4& t1, double* const (&tb)[2], int q, int c) {
-  gtile::lds_fence();
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    tb[0][(4 * s + q) * 17 + c] = t0[s];
-    tb[1][(4 * s + q) * 17 + c] = t1[s];
-  }
-  gtile::lds_fence();
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    t0[s] = tb[0][c * 17 + 4 * s + q];
-    t1[s] = tb[1][c * 17 + 4 * s + q];
-  }
-  gtile::lds_fence();
-}
 
 // gtile::to_row of two chains' column vectors through their own LDS rows, one round trip for both
 __device__ __forceinline__ void to_row2(const double (&v)[2], double* const (&vb)[2], gs_d4 (&o)[2], int q, int c) {
@@ -96,13 +57,10 @@ __device__ __forceinline__ void to_row2(const double (&v)[2], double* const (&vb
 
 // tile_elim1's column elimination on two chains at once (paired layout): on return B * rsd is U^-1 of
 // each chain's tile and A its column-eliminated tile, both paired; rsd the lane's chain's pivot^-1/2
-// of column c.  Same operations per element as tile_elim1<KMAX, PR>.
-struct gpair_nofill {
-  __device__ void operator()(int) const {}
-};
-template <int KMAX, bool PR, typename F = gpair_nofill>
-__device__ __forceinline__ void tile_elim_pair(double (&A)[8], double (&B)[8], double& rsd, int lane,
-                                               F&& fill = F()) {
+// of column c.  Same operations per element as tile_elim1<KMAX, PR>.  fill(k) is called once per pivot
+// step: independent work of the caller's for the step's dependency waits (the look-ahead updates).
+template <int KMAX, bool PR, typename F>
+__device__ __forceinline__ void tile_elim_pair(double (&A)[8], double (&B)[8], double& rsd, int lane, F&& fill) {
   using namespace gtile;
   using gpair::ptk;
   if constexpr (PR && GS_DIAG_PRIO > 0) __builtin_amdgcn_s_setprio(GS_DIAG_PRIO);
@@ -112,35 +70,26 @@ __device__ __forceinline__ void tile_elim_pair(double (&A)[8], double (&B)[8], d
   double akc = bcast_lane_bp(A[ptk(0)], base + c);  // row 0 of the lane's chain
 #pragma unroll
   for (int k = 0; k < KMAX; ++k) {
-    const int k1 = k >> 2;
     double rn = 0.0;
     if (k + 1 < KMAX) rn = bcast_lane_bp(A[ptk(k + 1)], base + 16 * ((k + 1) & 1) + c);
     __builtin_amdgcn_sched_barrier(0);
     const double akk = newbcast(akc, k);
     if (k + 1 < KMAX) {
-#if GS_EXEC_MASK
       const double akm = zero_cols_le(akc, k);
-#else
-      const double akm = (c > opq(k)) ? akc : 0.0;
-#endif
       const double i0 = __builtin_amdgcn_rcp(akk);
-#if GS_PIV_NR2
-      const double n1 = i0 * fma(akk, i0, -2.0);
-      const double ng = (akm * n1) * fma(akk, n1, 2.0);
-#else
       const double ng = (akm * i0) * fma(akk, i0, -2.0);
-#endif
       akc = fmac_nb(rn, rn, ng, k);
-      // registers holding a row >= k of A and <= k of B: from / up to ptk(k).  tile_elim1 also
-      // updates the register's other rows of the row group (rows < k of A: eliminated rows nothing
-      // reads again; rows > k of B: still identity rows, whose update adds ng x 0 = +-0 and leaves
-      // them unchanged for a finite ng), so every value read afterwards is the same
+      // only the registers holding a row >= k of A and <= k of B: from / up to ptk(k), one fmac fewer
+      // per step than tile_elim1's row-group granularity.  tile_elim1 also updates the register's other
+      // rows of the row group (rows < k of A: eliminated rows nothing reads again; rows > k of B: still
+      // identity rows, whose update adds ng x 0 = +-0 and leaves them unchanged for a finite ng), so
+      // every value read afterwards is the same
 #pragma unroll
-      for (int t = GS_PAIR_SKIP ? ptk(k) : 2 * k1; t < 8; ++t) A[t] = fmac_nb(A[t], A[t], ng, k);
+      for (int t = ptk(k); t < 8; ++t) A[t] = fmac_nb(A[t], A[t], ng, k);
 #pragma unroll
-      for (int t = 0; t <= (GS_PAIR_SKIP ? ptk(k) : 2 * k1 + 1); ++t) B[t] = fmac_nb(B[t], B[t], ng, k);
+      for (int t = 0; t <= ptk(k); ++t) B[t] = fmac_nb(B[t], B[t], ng, k);
     }
-    fill(k);  // GS_PAIR_LOOKAHEAD: independent work for this step's dependency waits
+    fill(k);
   }
   // A[ptk(c)] as a select tree on the bits of ptk(c) (a select chain on a lane-varying index is turned
   // into a private-array load, i.e. scratch)
@@ -208,11 +157,7 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
           const double v = Sl[(4 * ti + s) * 64];
 #pragma unroll
           for (int ch = 0; ch < 2; ++ch) {
-#if GS_EXEC_MASK
             t[ch][ti][s] = (I == J) ? add_on_diag(v, phc[ch][I], s) : v;
-#else
-            t[ch][ti][s] = v + ((I == J && 4 * s + q == c) ? phc[ch][I] : 0.0);
-#endif
           }
         }
       }
@@ -232,8 +177,9 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
       gpair::swap32(PA[2 * s], PA[2 * s + 1]);
     }
     double rsd;
-#if GS_PAIR_LOOKAHEAD
-    // the trailing updates of step K - 1 other than tile (K, K), one tile-op per elimination step
+    // Look-ahead: the trailing updates of step K - 1 other than tile (K, K) are issued inside this
+    // elimination, one tile-op per pivot step (each tile still sees its updates in K order, so the draws
+    // are unchanged bit for bit; at NT = 4 at most 10 tile-ops wait, fewer than the 16 steps)
     auto fill = [&](int k) {
       if (K == 0) return;
       int n = 0;
@@ -261,12 +207,6 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
 #pragma unroll
         for (int J = K; J < NT; ++J) t[ch][tix(K - 1, J, NT)] = transpose(t[ch][tix(K - 1, J, NT)], tb[ch], q, c);
     }
-#else
-    if (K == NT - 1)
-      tile_elim_pair<CP, PR>(PA, PB, rsd, lane);
-    else
-      tile_elim_pair<16, PR>(PA, PB, rsd, lane);
-#endif
     if (K == NT - 1) {
       // y_last[k] = (row CP of the eliminated tile)[k] * pivot_k^-1/2, k < CP, of the lane's chain,
       // then to each chain's column layout (every row group)
@@ -299,15 +239,8 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
         t[ch][tix(K, J, NT)] = mfma_tn(z, V[ch], t[ch][tix(K, J, NT)]);
       }
     }
-#if GS_PAIR_T2
-    t[0][kk] = V[0];
-    t[1][kk] = V[1];
-    transpose2(t[0][kk], t[1][kk], tb, q, c);
-#else
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) t[ch][kk] = transpose(V[ch], tb[ch], q, c);
-#endif
-#if GS_PAIR_LOOKAHEAD
     // only tile (K + 1, K + 1) now: the next elimination needs it; the rest go into its steps
     if (K + 1 < NT) {
 #pragma unroll
@@ -315,30 +248,10 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
         t[ch][tix(K + 1, K + 1, NT)] =
             mfma_tn_sub(t[ch][tix(K + 1, K + 1, NT)], t[ch][tix(K, K + 1, NT)], t[ch][tix(K, K + 1, NT)]);
     }
-#else
-#pragma unroll
-    for (int I = K + 1; I < NT; ++I)
-#pragma unroll
-      for (int J = I; J < NT; ++J)
-#pragma unroll
-        for (int ch = 0; ch < 2; ++ch)
-          t[ch][tix(I, J, NT)] = mfma_tn_sub(t[ch][tix(I, J, NT)], t[ch][tix(K, I, NT)], t[ch][tix(K, J, NT)]);
-#endif
-#if GS_PAIR_LOOKAHEAD
     // (row K's transposes follow the next elimination, after its last use by the pending updates)
-#elif GS_PAIR_T2
-#pragma unroll
-    for (int J = K + 1; J < NT; ++J) transpose2(t[0][tix(K, J, NT)], t[1][tix(K, J, NT)], tb, q, c);
-#else
-#pragma unroll
-    for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-      for (int J = K + 1; J < NT; ++J) t[ch][tix(K, J, NT)] = transpose(t[ch][tix(K, J, NT)], tb[ch], q, c);
-#endif
     if constexpr (PR && GS_UPD_PRIO > 0) __builtin_amdgcn_s_setprio(GS_BASE_PRIO);
   }
 
-#if GS_PAIR_SOLVE_ILV
   // ---- the solves and the fixed block of both chains interleaved step by step (each chain's
   // operations in the one-chain order); the LDS round trips of the row transposes and the fixed
   // block's G / R loads are shared
@@ -429,70 +342,4 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
     lds_fence();
     if constexpr (PR && GS_PAIR_FIX_PRIO > 0) __builtin_amdgcn_s_setprio(GS_BASE_PRIO);
   }
-#else
-  // ---- the solves and the fixed block, one chain after the other: chain a's tiles and solution rows
-  // are dead before chain b's solve needs its own (interleaving the two held ~250 VGPRs and spilled)
-#pragma unroll
-  for (int ch = 0; ch < 2; ++ch) {
-    // forward (augmented): y_K = column CP of U_K,last = row CP of the stored U_K,last^T
-    double ycol[NT];
-#pragma unroll
-    for (int K = 0; K + 1 < NT; ++K) ycol[K] = bcast_group_bp(t[ch][tix(K, NT - 1, NT)][CP >> 2], CP & 3, c);
-    ycol[NT - 1] = ylast[ch];
-
-    if constexpr (PR && GS_SOLVE_PRIO > 0) __builtin_amdgcn_s_setprio(GS_SOLVE_PRIO);
-    // backward: U x = y + zF
-    double xcol[NT];
-    gs_d4 xrow[NT];
-#pragma unroll
-    for (int K = NT - 1; K >= 0; --K) {
-      double p = 0.0;
-#pragma unroll
-      for (int J = K + 1; J < NT; ++J) {
-        const gs_d4 ut = t[ch][tix(K, J, NT)];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) p = fma(ut[s], xrow[J][s], p);
-      }
-      if (K + 1 < NT) p = qsum(p);
-      const gs_d4 sr = to_row(ycol[K] + ob[ch][16 * K + c] - p, vb[ch], q, c);
-      const gs_d4 W = t[ch][tix(K, K, NT)];
-      double p2 = 0.0;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) p2 = fma(W[s], sr[s], p2);
-      xcol[K] = qsum(p2);
-      xrow[K] = to_row(xcol[K], vb[ch], q, c);
-    }
-    lds_fence();
-#pragma unroll
-    for (int K = 0; K < NT; ++K) ob[ch][16 * K + c] = xcol[K];
-    lds_fence();
-    bF[ch] = (lane < NF) ? ob[ch][lane] : 0.0;
-    lds_fence();
-    if constexpr (PR && GS_SOLVE_PRIO > 0) __builtin_amdgcn_s_setprio(GS_BASE_PRIO);
-
-    if constexpr (PR && GS_PAIR_FIX_PRIO > 0) __builtin_amdgcn_s_setprio(GS_PAIR_FIX_PRIO);
-    // fixed-prior block x_M = h + R z_M - G x_F (tiled G' = -G and R', nM <= 16: one chunk); z_M was
-    // staged in the chain's zm slot before the factorisation
-    {
-      const int row = c;
-      const bool rok = row < nM;
-      double p = 0.0;
-      const double* Gl = M.G + lane + z0;
-#pragma unroll
-      for (int J = 0; J < NT; ++J)
-#pragma unroll
-        for (int s = 0; s < 4; ++s) p = fma(Gl[(4 * J + s) * 64], xrow[J][s], p);
-      const double* Rl = M.R + lane + z0;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) p = fma(Rl[s * 64], zm[ch][4 * s + q], p);
-      p = qsum(p);
-      const double xm = rok ? M.h[row + z0] + p : 0.0;
-      ob[ch][row] = xm;
-    }
-    lds_fence();
-    bM[ch] = (lane < nM) ? ob[ch][lane] : 0.0;
-    lds_fence();
-    if constexpr (PR && GS_PAIR_FIX_PRIO > 0) __builtin_amdgcn_s_setprio(GS_BASE_PRIO);
-  }
-#endif
 }

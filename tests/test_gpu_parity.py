@@ -356,21 +356,30 @@ def test_resume_many_chains(tmp_path, record_bchains):
         assert not np.array_equal(b[1:, 101:], a[1:, 101:])        # b of chains 1.. was redrawn
 
 
-def test_history_straight_to_pinned_host(model, replay):
+@pytest.mark.parametrize("sched", [2, 3])
+def test_history_straight_to_pinned_host(ctx, model, replay, sched):
     """Zero-copy history (sample()'s default): x rows and the first K chains' b rows written
     by the kernel into pinned host memory (GS_OPT_BREC_CHAINS) equal the HBM rows of the same
-    sweeps, bit for bit; the option is restored after the call."""
+    sweeps, bit for bit; the option is restored after the call.  With one chain per wave
+    (GS_OPT_SWEEP_SCHED = 2) and two (3: k_sweep_pair's compact record offsets)."""
     from pulsar_timing_gibbsspec_amd import _lib
     from pulsar_timing_gibbsspec_amd.engine import FreeSpectrumChains
     C, n, K = 8, 30, 2
     x0 = golden("single_j1713.npz")["x0"]
-    ra = FreeSpectrumChains(model, replay["rhomin"], replay["rhomax"], C, x0)
-    xa, ba = ra.run(n)
-    rb = FreeSpectrumChains(model, replay["rhomin"], replay["rhomax"], C, x0)
-    xh = torch.empty(n, C, 30, dtype=torch.float64, pin_memory=True)
-    bh = torch.empty(n, K, model.ldb, dtype=torch.float64, pin_memory=True)
-    rb.run(n, x_rec=xh, b_rec=bh, record_b_chains=K)
-    torch.cuda.synchronize()
+    prev = ctx.get_option(_lib.OPT_SWEEP_SCHED)
+    ctx.set_option(_lib.OPT_SWEEP_SCHED, sched)
+    try:
+        ra = FreeSpectrumChains(model, replay["rhomin"], replay["rhomax"], C, x0)
+        xa, ba = ra.run(n)
+        assert ctx.get_option(_lib.OPT_LAST_SWEEP_SHAPE) == sched
+        rb = FreeSpectrumChains(model, replay["rhomin"], replay["rhomax"], C, x0)
+        xh = torch.empty(n, C, 30, dtype=torch.float64, pin_memory=True)
+        bh = torch.empty(n, K, model.ldb, dtype=torch.float64, pin_memory=True)
+        rb.run(n, x_rec=xh, b_rec=bh, record_b_chains=K)
+        torch.cuda.synchronize()
+        assert ctx.get_option(_lib.OPT_LAST_SWEEP_SHAPE) == sched
+    finally:
+        ctx.set_option(_lib.OPT_SWEEP_SCHED, prev)
     assert model.ctx.get_option(_lib.OPT_BREC_CHAINS) == 0
     assert torch.equal(xh, xa.cpu())
     assert torch.equal(bh, ba.cpu()[:, :K])
@@ -466,6 +475,55 @@ def test_sweep_two_chains_per_wave_equal_one_chain_per_wave(ctx, model, replay, 
     assert shapes == [2, 3]                      # the kernels that ran: one chain per wave, two
     for a, b in zip(*out):
         assert np.array_equal(a, b)
+    assert not out[1][-1].any()
+
+
+def test_sweep_two_chains_per_wave_three_pulsars(ctx):
+    """k_sweep_pair on more than one pulsar with a non-zero global pulsar index: three consecutive
+    pulsars of the simulated `indep` array (models built as tests/test_gpu_indep.py::_model does), the
+    first run of three whose timing models all have nM <= 16 columns (the pair kernel's tiled fixed
+    block), GS_OPT_PSR_BASE at their first index, 6 chains each, 5 sweeps and a continued second
+    launch: GS_OPT_SWEEP_SCHED = 3 gives bit for bit the recorded rows and final state of 2."""
+    from pulsar_timing_gibbsspec_amd import _lib, synthetic
+    from pulsar_timing_gibbsspec_amd.engine import DeviceModel, FreeSpectrumChains
+    ptas = synthetic.pulsar_ptas(synthetic.array_pta(kind="indep", seed=0))
+    T = [p.get_basis()[0] for p in ptas]
+    N = [p.get_ndiag({})[0] for p in ptas]
+    R = [p.get_residuals()[0] for p in ptas]
+
+    def build(lo, hi):
+        return DeviceModel(ctx, T[lo:hi], N[lo:hi], R[lo:hi], [np.arange(60)] * (hi - lo),
+                           [np.full(t.shape[1] - 60, 1e-40) for t in T[lo:hi]])
+
+    nM = build(0, len(T)).m - 60
+    runs = [p for p in range(len(nM) - 2) if (nM[p:p + 3] <= 16).all()]
+    assert runs
+    lo = runs[0]
+    C, S = 6, 5
+    x0 = np.random.default_rng(9).uniform(-9, -4, (3 * C, 30))
+    out, shapes = [], []
+    prev = ctx.get_option(_lib.OPT_SWEEP_SCHED)
+    ctx.set_option(_lib.OPT_PSR_BASE, lo)
+    try:
+        model3 = build(lo, lo + 3)
+        for sched in (2, 3):
+            ctx.set_option(_lib.OPT_SWEEP_SCHED, sched)
+            run = FreeSpectrumChains(model3, 1e-18, 1e-8, C, x0)
+            xr, br = run.run(S)
+            xr2, br2 = run.run(S)
+            shapes.append(ctx.get_option(_lib.OPT_LAST_SWEEP_SHAPE))
+            out.append([t.cpu().numpy() for t in (xr, br, xr2, br2, run.x, run.b, run.info)])
+    finally:
+        ctx.set_option(_lib.OPT_SWEEP_SCHED, prev)
+        ctx.set_option(_lib.OPT_PSR_BASE, 0)
+    assert shapes == [2, 3]
+    for a, b in zip(*out):
+        if a.shape[-1] == model3.ldb:            # b rows: columns >= m_p are never written
+            for p in range(3):
+                rows, m = slice(p * C, (p + 1) * C), model3.m[p]
+                assert np.array_equal(a[..., rows, :m], b[..., rows, :m])
+        else:
+            assert np.array_equal(a, b)
     assert not out[1][-1].any()
 
 
