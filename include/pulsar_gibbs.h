@@ -409,6 +409,20 @@ int gs_phi_from_x(gs_ctx* ctx, int n_chain, int ncol, const double* x, int ldx, 
  *   over (sin, cos); gw_col [n_f], red_col [n_psr x n_f] or NULL.
  */
 int gs_pta_record(gs_ctx* ctx, int n_chain, int n_param, const double* x, double* x_rec, double* xlast);
+/*
+ * gs_pta_record for a block of sweeps recorded chain-major, into a slot the device selects:
+ *   slots[*slot_sel][c * chain_stride + row_off + j] = x[c][j],  c < n_rec, j < n_param,
+ *   xlast[c] = x[c][n_param-1]                                   for every c < n_chain.
+ * slots (two base pointers) and slot_sel (0 or 1) live in device memory and are read by the
+ * kernel, as the sweep counter of gs_ctx_set_sweep_counter is: a captured graph of a block of
+ * sweeps (row_off = kept row * n_param, chain_stride = block rows * n_param) double-buffers when
+ * the host flips *slot_sel between replays.  The slots may be device memory or pinned host
+ * memory (written over PCIe).  n_rec = 0 writes xlast only (slots and slot_sel may be NULL):
+ * the sweeps a thinned history drops.  Needs n_rec <= n_chain and, when n_rec > 0,
+ * 0 <= row_off <= chain_stride - n_param; the caller sizes each slot to n_rec * chain_stride.
+ */
+int gs_pta_record_block(gs_ctx* ctx, int n_chain, int n_param, const double* x, int n_rec, int64_t chain_stride,
+                        int64_t row_off, double* const* slots, const int* slot_sel, double* xlast);
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate);

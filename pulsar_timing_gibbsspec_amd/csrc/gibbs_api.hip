@@ -765,6 +765,22 @@ int gs_pta_record(gs_ctx* ctx, int n_chain, int n_param, const double* x, double
   return after_launch("k_pta_record");
 }
 
+int gs_pta_record_block(gs_ctx* ctx, int n_chain, int n_param, const double* x, int n_rec, int64_t chain_stride,
+                        int64_t row_off, double* const* slots, const int* slot_sel, double* xlast) {
+  if (!ctx) return fail_arg(1, "ctx is NULL");
+  if (n_chain < 0 || n_param <= 0) return fail_arg(2, "bad size");
+  if (!x || !xlast) return fail_arg(4, "NULL array");
+  if (n_rec < 0 || n_rec > n_chain) return fail_arg(5, "n_rec must be in [0, n_chain]");
+  if (n_rec > 0) {
+    if (chain_stride < n_param) return fail_arg(6, "chain_stride must be >= n_param");
+    if (row_off < 0 || row_off > chain_stride - n_param)
+      return fail_arg(7, "row_off must leave a whole row inside chain_stride");
+    if (!slots || !slot_sel) return fail_arg(8, "NULL slots / slot_sel");
+  }
+  launch_pta_record_block(ctx->stream, n_chain, n_param, x, n_rec, chain_stride, row_off, slots, slot_sel, xlast);
+  return after_launch("k_pta_record_block");
+}
+
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate) {

@@ -1464,6 +1464,29 @@ __global__ void k_pta_record(int n_chain, int n_param, const double* x, double* 
   if ((t % n_param) == n_param - 1) xlast[t / n_param] = x[t];
 }
 
+// block record: chain c < n_rec writes its row into the slot the DEVICE selects,
+//   slots[*slot_sel & 1][c * chain_stride + row_off + j] = x[c][j],
+// and every chain writes xlast as k_pta_record does.  slots and slot_sel are read here, not
+// baked into the launch, so one captured graph alternates between two destinations (HBM or
+// pinned host memory) when the host flips *slot_sel between replays.  A row is padded to whole
+// waves (npad = 64 ceil(n_param / 64)): a wave moves one 512-byte run of one chain, lane i at
+// base + 8 i; rows are only 8-byte aligned (n_param may be odd), so the accesses stay 8 bytes
+// wide.
+__global__ void k_pta_record_block(int n_chain, int n_param, int npad, const double* x, int n_rec,
+                                   int64_t chain_stride, int64_t row_off, double* const* slots,
+                                   const int* slot_sel, double* xlast) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t c = t / npad;
+  const int j = (int)(t % npad);
+  if (c >= n_chain || j >= n_param) return;
+  const double v = x[c * n_param + j];
+  if (c < n_rec) {
+    double* dst = slots[*slot_sel & 1];
+    dst[c * chain_stride + row_off + j] = v;
+  }
+  if (j == n_param - 1) xlast[c] = v;
+}
+
 // gate[c] = all_j x[c][j] != xlast[c]  (pta_gibbs.py:703); one wavefront per chain.
 // phiinv_F[p*n_chain + c][2k + {0,1}] = 1 / (10**(2 x_gw[k]) + 10**(2 x_red[p][k]))
 __global__ void k_pta_gate_phiinv(PtaGateArgs A) {
@@ -1635,6 +1658,17 @@ int launch_pta_record(hipStream_t s, int n_chain, int n_param, const double* x, 
   const int64_t n = (int64_t)n_chain * n_param;
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_pta_record, grid1(n, 256), dim3(256), 0, s, n_chain, n_param, x, x_rec, xlast);
+  return 0;
+}
+
+int launch_pta_record_block(hipStream_t s, int n_chain, int n_param, const double* x, int n_rec,
+                            int64_t chain_stride, int64_t row_off, double* const* slots, const int* slot_sel,
+                            double* xlast) {
+  const int npad = (n_param + 63) / 64 * 64;
+  const int64_t n = (int64_t)n_chain * npad;
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_pta_record_block, grid1(n, 256), dim3(256), 0, s, n_chain, n_param, npad, x, n_rec,
+                     chain_stride, row_off, slots, slot_sel, xlast);
   return 0;
 }
 

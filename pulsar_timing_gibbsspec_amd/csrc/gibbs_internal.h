@@ -218,6 +218,9 @@ int launch_rho_gumbel(hipStream_t s, const GridArgs& a);
 int launch_phi_from_x(hipStream_t s, int n_chain, int ncol, const double* x, int ldx, const int32_t* cols,
                       double* out);
 int launch_pta_record(hipStream_t s, int n_chain, int n_param, const double* x, double* x_rec, double* xlast);
+int launch_pta_record_block(hipStream_t s, int n_chain, int n_param, const double* x, int n_rec,
+                            int64_t chain_stride, int64_t row_off, double* const* slots, const int* slot_sel,
+                            double* xlast);
 int launch_pta_gate_phiinv(hipStream_t s, const PtaGateArgs& a);
 int launch_phi_powerlaw(hipStream_t s, int n_psr, int n_chain, int n_f, const double* x, int ldx,
                         const int32_t* pl_col, const double* lnphi, double* out);

@@ -349,7 +349,10 @@ class HistoryStreamer:
         and no staging in HBM.  Measured on MI355X for the configs[1] headline (x rows of
         4096 chains, 98 MB per 100 sweeps): 2.97 ms per 100-sweep block written straight
         to the host vs 2.73 ms into HBM and 4.2 ms with the copy overlapped on a side stream
-        (tools/stream_probe.py)."""
+        (tools/stream_probe.py).  For the PTA's chain-major blocks (BlockRecorder: 2048 chains x
+        100 sweeps x 1380 parameters, 2.26 GB per block, tools/sample_rate.py) the two tie:
+        0.812 s per block written straight to the host vs 0.795 s through HBM slots and the side
+        stream, both bound by the host's file work (profiles/sample_stream/SUMMARY.md)."""
         dev = ctx.device
         self.ctx = ctx
         n = len(shapes)
@@ -364,10 +367,20 @@ class HistoryStreamer:
         self.done = [torch.cuda.Event(), torch.cuda.Event()]
         self.rows = [0, 0]
 
-    def buffers(self, slot, n):
+    def buffers(self, slot, n=None):
+        """The record buffers of a slot (n: their first n rows; None: whole)."""
         return [b[:n] for b in self.dev_bufs[slot]]
 
-    def submit(self, slot, n):
+    def slot_table(self, i):
+        """Device int64 [2]: the base addresses of buffer i's two slots (HBM, or the pinned host
+        slots when direct) -- the ``slots`` argument of gs_pta_record_block, with which one
+        captured graph writes the slot a device flag selects."""
+        return torch.tensor([self.dev_bufs[s][i].data_ptr() for s in (0, 1)], dtype=torch.int64,
+                            device=self.ctx.device)
+
+    def submit(self, slot, n=None):
+        """Queue the slot's copies behind the work launched so far (n: first n rows of every
+        buffer; None: the whole buffers, e.g. blocks that are not laid out rows first)."""
         ready = torch.cuda.Event()
         ready.record(self.ctx.stream)
         with torch.cuda.stream(self.side):
@@ -381,6 +394,46 @@ class HistoryStreamer:
     def fetch(self, slot):
         self.done[slot].synchronize()
         return [h[:self.rows[slot]] for h in self.host_bufs[slot]]
+
+
+class BlockRecorder:
+    """Chain-major record of blocks of PTAChains sweeps into the two slots of a HistoryStreamer.
+
+    A slot holds one block, [n_rec, rows, n_param]: the first n_rec chains, the sweeps ii of the
+    block with ii % thin == 0 (at most ``rows`` of them) -- the layout of chains.npy, so the host
+    never transposes.  The slot is selected on the DEVICE (``sel``, read by gs_pta_record_block),
+    so a graph captured once (PTAChains.capture(n, recorder=...)) alternates between the slots:
+    ``select(slot)`` is a stream-ordered fill the host queues before each replay.  ``direct``:
+    the slots are pinned host memory the kernel writes over PCIe (no copy); otherwise HBM, copied
+    by the streamer's side stream.  extra: further per-block buffers the streamer carries (e.g.
+    the sampler state of a save point), never direct."""
+
+    def __init__(self, ctx, n_rec, rows, n_param, thin=1, direct=True, extra=()):
+        self.ctx, self.n_rec, self.rows = ctx, int(n_rec), int(rows)
+        self.n_param, self.thin = int(n_param), int(thin)
+        self.streamer = HistoryStreamer(ctx, [(self.n_rec, self.rows, self.n_param)] + list(extra),
+                                        direct=[bool(direct)] + [False] * len(extra))
+        self.slots = self.streamer.slot_table(0)
+        self.sel = torch.zeros(1, dtype=torch.int32, device=ctx.device)
+
+    def row_of(self, first, ii):
+        """Row of sweep ii in a block whose first sweep is ``first`` (None: thinned out)."""
+        if ii % self.thin:
+            return None
+        row = ii // self.thin - -(-first // self.thin)        # kept sweeps in [first, ii)
+        if not 0 <= row < self.rows:
+            raise ValueError(f"sweep {ii} of the block starting at {first} has no row in a slot of {self.rows}")
+        return row
+
+    def select(self, slot):
+        with torch.cuda.stream(self.ctx.stream):
+            self.sel.fill_(int(slot))
+
+    def record(self, eng, row):
+        n_rec = self.n_rec if row is not None else 0
+        check(self.ctx.lib.gs_pta_record_block(
+            self.ctx.handle, eng.C, eng.n_param, ptr(eng.x), n_rec, self.rows * self.n_param,
+            (row or 0) * self.n_param, ptr(self.slots), ptr(self.sel), ptr(eng.xlast)), "gs_pta_record_block")
 
 
 def grid3(rhomin, rhomax, n=1000, device="cuda"):
@@ -582,13 +635,17 @@ class PTAChains:
         h.steps(self.x, nsteps, self.it, self.chain_base, inj=inj, q_rec=q_rec)
         h.fresh = False
 
-    def sweep_begin(self, x_rec=None, z0=None, u_red=None, mh_inj=None):
+    def sweep_begin(self, x_rec=None, z0=None, u_red=None, mh_inj=None, block_rec=None):
         """Record, [first draw], [hyper MH], tau and the local red draws.  Returns the local
-        exchange slab [P_local, 1 or 2, n_f, C] (None when not sharded)."""
+        exchange slab [P_local, 1 or 2, n_f, C] (None when not sharded).  block_rec
+        (BlockRecorder, kept row or None): record through gs_pta_record_block instead of x_rec."""
         lib, h, m = self.ctx.lib, self.ctx.handle, self.model
         ii = self.it
-        check(lib.gs_pta_record(h, self.C, self.n_param, ptr(self.x), ptr(x_rec), ptr(self.xlast)),
-              "gs_pta_record")
+        if block_rec is not None:
+            block_rec[0].record(self, block_rec[1])
+        else:
+            check(lib.gs_pta_record(h, self.C, self.n_param, ptr(self.x), ptr(x_rec), ptr(self.xlast)),
+                  "gs_pta_record")
         if ii == 0 or self.redraw_b:                           # pta_gibbs.py:669-670
             if self.hyper_pl or self.red_cond:
                 self._update_irn()
@@ -677,22 +734,25 @@ class PTAChains:
             acc = allreduce_sum(acc.clone(), group=getattr(self.gather, "group", None))
         return (acc / max(1, self.hyper.steps_total)).cpu().numpy()
 
-    def check_fx(self):
+    def check_fx(self, ovf=None):
         """curn_mode='sum': raise if gs_tau_sum_fx_b saw a tau it cannot sum exactly (negative,
         non-finite or >= rhomin_gw * 2^80, the fixed-point window) since the engine was built:
-        S would then be wrong.  Syncs."""
-        if self.curn_mode == "sum" and int(self.fx_ovf.item()):
+        S would then be wrong.  Syncs, unless ``ovf`` gives a value of the flag already fetched."""
+        if self.curn_mode == "sum" and int(self.fx_ovf.item() if ovf is None else ovf):
             raise RuntimeError("curn_mode='sum': a tau fell outside the fixed-point window (negative, "
                                "non-finite or >= rhomin_gw * 2**80); rerun with curn_mode='exact'")
 
-    def capture(self, n_sweeps):
+    def capture(self, n_sweeps, recorder=None):
         """Capture n_sweeps steady-state sweeps (device Philox) into a hipGraph
         (torch.cuda.CUDAGraph around the C-ABI launches on the context's stream).
 
         Philox counters take sweep = launch argument + a device counter
         (gs_ctx_set_sweep_counter), which the graph advances itself (gs_counter_add),
         so every replay draws the next n_sweeps sweeps: replays are bit-identical to
-        eager sweeps.  The graph records x into ``graph_rec`` (n_sweeps, C, n_param).
+        eager sweeps.  The graph records x into ``graph_rec`` (n_sweeps, C, n_param), or, with a
+        ``recorder`` (BlockRecorder), chain-major into the recorder's slot that its device flag
+        selects at replay (sweep ii of the block -> the recorder's row for it, or xlast alone
+        where the recorder thins it out); there is no ``graph_rec`` then.
 
         A pulsar-sharded engine captures its per-sweep exchange too: the RCCL all-reduce of
         the fixed-point tau-sum digits (or the [tau | x_red] all-gather) is issued on the
@@ -708,7 +768,8 @@ class PTAChains:
                                           "(RCCL) backend; gloo collectives run on the host")
         lib, h, dev = self.ctx.lib, self.ctx.handle, self.ctx.device
         n = int(n_sweeps)
-        self.graph_rec = torch.empty(n, self.C, self.n_param, dtype=torch.float64, device=dev)
+        self.graph_rec = torch.empty(n, self.C, self.n_param, dtype=torch.float64, device=dev) \
+            if recorder is None else None
         self._gcount = torch.zeros(1, dtype=torch.int64, device=dev)
         self._gbase, self._gn = self.it, n
         cap = torch.cuda.Stream(device=dev)
@@ -723,7 +784,10 @@ class PTAChains:
         try:
             with torch.cuda.graph(self.graph, stream=cap):
                 for i in range(n):
-                    self.sweep(x_rec=self.graph_rec[i])
+                    if recorder is None:
+                        self.sweep(x_rec=self.graph_rec[i])
+                    else:
+                        self.sweep(block_rec=(recorder, recorder.row_of(self._gbase, self.it)))
                 check(lib.gs_counter_add(h, ptr(self._gcount), n), "gs_counter_add")
         finally:
             check(lib.gs_ctx_set_sweep_counter(h, None), "gs_ctx_set_sweep_counter")
@@ -735,7 +799,8 @@ class PTAChains:
         return self.graph_rec
 
     def replay(self):
-        """Run the captured sweeps once (the next n_sweeps sweeps); returns graph_rec."""
+        """Run the captured sweeps once (the next n_sweeps sweeps); returns graph_rec (None when
+        the graph records through a BlockRecorder)."""
         self._gcount.fill_(self.it - self._gbase)   # stays right if eager sweeps ran between
         self.graph.replay()
         self.it += self._gn
@@ -743,13 +808,14 @@ class PTAChains:
             self.hyper.steps_total += self._g_hsteps
         return self.graph_rec
 
-    def sweep(self, x_rec=None, z0=None, z=None, u_red=None, u_curn=None, mh_inj=None):
-        """One PTABlockGibbs sweep for every chain; x_rec: (n_chain, n_param) row or None.
+    def sweep(self, x_rec=None, z0=None, z=None, u_red=None, u_curn=None, mh_inj=None, block_rec=None):
+        """One PTABlockGibbs sweep for every chain; x_rec: (n_chain, n_param) row or None;
+        block_rec: (BlockRecorder, row in the block or None) records chain-major instead.
         z0/z: (P*n_chain, ldb) injected normals (original column order); u_red
         (n_chain, P, n_f) and u_curn (n_chain, n_f): injected uniforms; mh_inj (steps, n_chain,
         4): injected hyper-MH draws (scale, j, randn, rand)."""
         with fail_counts(self.ctx, self.fail_count):
-            slab = self.sweep_begin(x_rec=x_rec, z0=z0, u_red=u_red, mh_inj=mh_inj)
+            slab = self.sweep_begin(x_rec=x_rec, z0=z0, u_red=u_red, mh_inj=mh_inj, block_rec=block_rec)
             if self.sharded:
                 # the collective is ordered after the slab's kernels: torch issues it against the
                 # CURRENT stream, which is made the context's (the kernels' stream; a no-op when the

@@ -302,12 +302,37 @@ class PTABlockGibbs(object):
         return st
 
     # ------------------------------------------------------------ loop
-    def sample(self, xs, outdir="./", niter=10000, resume=False, save_every=100, *, flush_final=False):
+    def sample(self, xs, outdir="./", niter=10000, resume=False, save_every=100, *, flush_final=False,
+               history="memory", record_chains=None, thin=1, slots="host"):
         """PTABlockGibbs.sample (pta_gibbs.py:631-713): chain row ii = state before sweep ii;
         chain.txt (chain 0) rewritten with rows [:ii+1] at ii % 100 == 0, ii > 0;
         with nchains > 1 also chains.npy (leading chain axis).  flush_final=True also
         writes the rows after the last multiple of save_every (the reference
-        drops them, Appendix A.8)."""
+        drops them, Appendix A.8).
+
+        history="memory" (default): every chain's history is kept on the host
+        (nchains x niter x npar doubles) and the files are rewritten at every save point.
+
+        history="disk": the same sweeps, streamed.  Whole blocks of save_every sweeps are replays
+        of one captured graph that records chain-major into two alternating slots
+        (engine.BlockRecorder; slots="host": pinned host memory the kernel writes, "device": HBM
+        slots copied by a side stream); each block is fetched one block behind the launch and
+        appended to the files (chain_writer.ChainWriter).  record_chains=K keeps chains 0..K-1
+        (default all), thin=t the sweeps ii % t == 0 (save_every % t == 0).  ``self.chains`` is the
+        memory map of chains.npy, shape (K, ceil(niter / t), npar), created at its final size: rows
+        beyond the count in gibbs_state.npz (``rows`` sweeps -> ceil(rows / t) rows) are UNWRITTEN.
+        chain.txt grows by append and holds the kept rows of chain 0; with thin=1 its bytes are
+        those of the default mode.  ``self.chain`` (returned) is chain 0's kept rows,
+        (ceil(niter / t), npar).  Host memory does not grow with nchains x niter: two pinned slots
+        of K x save_every / t x npar doubles, two pinned copies of the save-point state (x, b),
+        chain 0's history and one block's text."""
+        if history not in ("memory", "disk"):
+            raise ValueError("history must be 'memory' or 'disk'")
+        if history == "disk":
+            return self._sample_disk(xs, outdir, int(niter), resume, int(save_every), flush_final,
+                                     record_chains, thin, slots)
+        if record_chains is not None or thin != 1:
+            raise ValueError("record_chains and thin need history='disk'")
         print(f"Creating chain directory: {outdir}")
         os.makedirs(outdir, exist_ok=True)
         self._check_supported()
@@ -388,6 +413,151 @@ class PTABlockGibbs(object):
             if nc > 1:
                 np.save(f"{outdir}/chains.npy", self.chains[:, :self.iter + 1])
             self._save_state(outdir, self.iter + 1, eng)
+        b = eng.b.cpu().numpy()
+        self._b = [b[p * eng.C, :eng.model.m[p]] for p in range(eng.P)]
+        if eng.hyper is not None:
+            self.aclength_hyper = eng.hyper_acl
+            self.hyper_acceptance = eng.hyper.acceptance()
+        return self.chain
+
+    def _sample_disk(self, xs, outdir, niter, resume, save_every, flush_final, record_chains, thin, slots):
+        """sample(history="disk"): see sample.  Blocks are the default mode's -- sweep 0, then
+        (k S, (k + 1) S] for S = save_every, then the rest -- so save points and rows agree."""
+        from .chain_writer import ChainWriter
+        from .engine import BlockRecorder
+        nc, npar, S = self.nchains, len(xs), save_every
+        K = nc if record_chains is None else record_chains
+        for name, v in (("record_chains", K), ("thin", thin)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer (got {v!r})")
+        K, t = int(K), int(thin)
+        if not 1 <= K <= nc:
+            raise ValueError(f"record_chains must be in 1..nchains = {nc} (got {K})")
+        if t < 1 or S < 1 or S % t:
+            raise ValueError(f"thin must be positive and divide save_every (thin={t}, save_every={S})")
+        if slots not in ("host", "device"):
+            raise ValueError("slots must be 'host' or 'device'")
+        print(f"Creating chain directory: {outdir}")
+        os.makedirs(outdir, exist_ok=True)
+        self._check_supported()
+        nrows = -(-niter // t)
+        self.chain = np.zeros((nrows, npar))
+        self.iter = 0
+        start = 0
+        x0 = np.asarray(xs, float)
+        state = None
+        if resume and os.path.exists(f"{outdir}/chain.txt"):
+            print("Resuming from previous run...")
+            if os.path.exists(f"{outdir}/gibbs_state.npz"):
+                writer = ChainWriter(outdir, K, nrows, npar, thin=t, resume=True)
+                state = writer.state
+                if "x" not in state or state["x"].shape != (nc, npar):
+                    raise ValueError(f"cannot resume: gibbs_state.npz is not the state of {nc} chains of "
+                                     f"{npar} parameters")
+                start = int(state["rows"])
+                self.chain[:writer.rows_written] = writer.chains[0, :writer.rows_written]
+            else:
+                # only chain.txt (e.g. written by the reference): every row of chain 0, no thinning
+                prev = np.atleast_2d(np.loadtxt(f"{outdir}/chain.txt"))
+                if t != 1:
+                    raise ValueError("resuming from chain.txt alone needs thin=1")
+                writer = ChainWriter(outdir, K, nrows, npar, adopt=prev)
+                start = prev.shape[0]
+                self.chain[:start] = prev
+                x0 = prev[-1]
+        else:
+            writer = ChainWriter(outdir, K, nrows, npar, thin=t)
+        self.chains = writer.chains
+        eng = self._new_engine(x0)
+        self._engine = eng
+        dev = self.ctx.device
+        # per block and slot: the chain-major rows, the state of a save point (x, b) and
+        # [fx overflow flag, failed b draws so far]
+        rec = BlockRecorder(self.ctx, K, S // t, npar, thin=t, direct=slots == "host",
+                            extra=[tuple(eng.x.shape), tuple(eng.b.shape), (2,)])
+        st = rec.streamer
+        tstart = time.time()
+        ii = start
+        seen_fail = 0
+        if start > 0:
+            eng.it = start
+            if eng.hyper is not None and eng.hyper_acl is None:
+                if state is not None and "aclength_hyper" in state:
+                    eng.hyper_acl = int(state["aclength_hyper"])
+                else:
+                    raise NotImplementedError("resuming a redsample='mh' run needs aclength_hyper (set the "
+                                              "attribute, or keep gibbs_state.npz)")
+            if state is not None:
+                eng.x.copy_(torch.as_tensor(state["x"], device=dev))
+                eng.b.copy_(torch.as_tensor(state["b"], device=dev))
+            else:
+                eng.redraw_b = True            # as the default mode: draw b | x first
+
+        def drain(blk):
+            """Fetch a launched block (waits for that block only), check it, file it."""
+            nonlocal seen_fail
+            slot, i0, i1, save = blk
+            rows, x_h, b_h, flags = st.fetch(slot)
+            eng.check_fx(ovf=int(flags[0]))        # curn_mode='sum': tau inside the fixed-point window
+            nfail = int(flags[1])                  # failed (non-PD) b draws, b kept
+            if nfail > seen_fail:
+                print(f"WARNING: sweeps {i0}..{i1 - 1}: {nfail - seen_fail} b draws hit a non-positive-definite "
+                      "Sigma; those systems KEEP their previous b -- unlike the reference, whose LinAlgError "
+                      "branch (pta_gibbs.py:539-544) redraws b from a QR/SVD of Sigma with the wrong covariance "
+                      "(SURVEY Appendix A.7)")
+                seen_fail = nfail
+            r0, r1 = -(-i0 // t), -(-i1 // t)      # the kept sweeps of [i0, i1)
+            rows = rows.numpy()[:, :r1 - r0]
+            self.chain[r0:r1] = rows[0]
+            self.iter = last = i1 - 1
+            if save:
+                if last % S == 0:
+                    sys.stdout.write("\r")
+                    sys.stdout.write("Finished %g percent in %g seconds." % (last / niter * 100,
+                                                                               time.time() - tstart))
+                    sys.stdout.flush()
+                extra = {} if eng.hyper is None else {"aclength_hyper": eng.hyper_acl}
+                writer.append(rows, state=dict(rows=i1, x=x_h.numpy(), b=b_h.numpy(), **extra))
+            elif last == 0:
+                writer.append(rows, commit=False)  # row 0 is filed with the first save point
+
+        pending = None
+        slot = 0
+        captured = False
+        while ii < niter:
+            nxt = 1 if ii == 0 else min(niter, ((ii - 1) // S + 1) * S + 1)
+            save = ((nxt - 1) % S == 0 and nxt > 1) or (flush_final and nxt == niter)
+            whole = ii > 0 and (ii - 1) % S == 0 and nxt - ii == S and not eng.redraw_b
+            if whole and not captured:
+                if pending is not None:            # nothing in flight while the graph is captured
+                    drain(pending)
+                    pending = None
+                eng.capture(S, recorder=rec)
+                captured = True
+            rec.select(slot)
+            if whole:
+                eng.replay()
+            else:
+                for _ in range(nxt - ii):
+                    eng.sweep(block_rec=(rec, rec.row_of(ii, eng.it)))
+            with torch.cuda.stream(eng.ctx.stream):
+                _, x_d, b_d, fl_d = st.buffers(slot)
+                if save:
+                    x_d.copy_(eng.x)
+                    b_d.copy_(eng.b)
+                fl_d[0:1].copy_(eng.fx_ovf)
+                fl_d[1:2].copy_(eng.fail_count.sum(dtype=torch.float64).view(1))
+            st.submit(slot)
+            # the previous block is read while this one runs: its checks lag one block and no
+            # sync sits between two replays
+            if pending is not None:
+                drain(pending)
+            pending = (slot, ii, nxt, save)
+            slot ^= 1
+            ii = nxt
+        if pending is not None:
+            drain(pending)
+        writer.close()
         b = eng.b.cpu().numpy()
         self._b = [b[p * eng.C, :eng.model.m[p]] for p in range(eng.P)]
         if eng.hyper is not None:
