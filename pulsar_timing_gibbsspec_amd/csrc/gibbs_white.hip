@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256) void k_white_tnt(WhiteTntArgs A) {
     for (int r = 0; r < 4; ++r) {
       const double v = acc[r] + red[0][r][l] + red[1][r][l] + red[2][r][l];
       const int row = bi * 16 + (l >> 4) + 4 * r, col = bj * 16 + (l & 15);
-      if (row < m && col < m) {
+      if (row < m && col < m && (bi != bj || col <= row)) {  // diagonal tile: lower element only (exact symmetry)
         out[(int64_t)row * m + col] = v;
         out[(int64_t)col * m + row] = v;
       }
@@ -545,8 +545,12 @@ __global__ __launch_bounds__(64 * SY_WAVES) void k_white_syrk(WhiteTntArgs A) {
       const int row = bi * 16 + k + 4 * r, col = bj * 16 + i;
       const double v = v4[r];
       if (row < m && col < m) {
-        out[(int64_t)row * m + col] = v;
-        out[(int64_t)col * m + row] = v;
+        // a diagonal tile holds both (row, col) and (col, row), rounded differently (the 1/N scaling is
+        // on the A operand only): lower element only, or the two mirrored stores leave TNT asymmetric
+        if (bi != bj || col <= row) {
+          out[(int64_t)row * m + col] = v;
+          out[(int64_t)col * m + row] = v;
+        }
       } else if (row == m && col < m) {
         dout[col] = v;
       }

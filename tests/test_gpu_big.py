@@ -16,6 +16,7 @@ import pytest
 from oracle import gibbs_oracle as O
 from tests.conftest import gpu_available
 from tests.parity_data import exact_chol_draw, normwise_rel
+from tests.white_ref import check_tnt, exact_N, params_of
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +34,10 @@ def _white_N(d, p, x):
     ef = x[[2 * k for k in range(nb)]]
     eq = x[[2 * k + 1 for k in range(nb)]]
     return O.ndiag_white(d["sigma"][p], d["backend"][p], ef, eq)
+
+
+def _exact_N(d, p, x):
+    return exact_N(d["sigma"][p] ** 2, d["backend"][p], params_of(d["white"], x))
 
 
 @pytest.mark.parametrize("n_f", [40, 100, 104])
@@ -110,6 +115,8 @@ def test_syrk_tnt_per_system(ctx, n_tm, n_toa):
             TNTd, ddd = wm.tnt_host(p, c)
             assert np.max(np.abs(TNTd - TNT)) <= 1e-12 * np.max(np.abs(TNT))
             assert normwise_rel(ddd, dd) < 1e-12
+            # entrywise (n + 16) u sqrt(TNT_ii TNT_jj) against the long-double TNT, exact symmetry
+            check_tnt(TNTd, ddd, d["T"][p], _exact_N(d, p, x[p * C + c]), d["r"][p])
     assert int(wm.pinfo.abs().sum()) == 0
 
 
@@ -214,6 +221,7 @@ def test_full_size_config4_pulsar(ctx):
         TNTd, ddd = wm.tnt_host(0, c)
         assert np.max(np.abs(TNTd - TNT)) <= 1e-12 * np.max(np.abs(TNT))
         assert normwise_rel(ddd, dd) < 1e-12
+        check_tnt(TNTd, ddd, T, _exact_N(d, 0, x[c]), r)
     # b draw at the full size, fixed white noise (sigma^2), injected normals
     N = d["sigma"][0] ** 2
     model = DeviceModel(ctx, [T], [N], [r], [d["fidx"]], [d["phiinv_fixed"]])

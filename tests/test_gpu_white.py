@@ -13,6 +13,7 @@ import pytest
 from tests.conftest import golden, gpu_available
 from oracle import gibbs_oracle as O
 from tests.parity_data import exact_chol_draw, normwise_rel, white_params, white_replay
+from tests.white_ref import check_tnt, exact_N, params_of
 
 pytestmark = pytest.mark.gpu
 
@@ -58,6 +59,10 @@ def test_white_tnt_and_resid(ctx):
         TNTd, dd = wm.tnt_host(0, c)
         assert np.max(np.abs(TNTd - TNT)) <= 1e-12 * np.max(np.abs(TNT))
         assert normwise_rel(dd, d) < 1e-12
+        # entrywise against the long-double TNT at the exact N, and exact symmetry: TNT spans many
+        # decades (timing-model against Fourier columns), which the normwise check above cannot see
+        check_tnt(TNTd, dd, g["T"], exact_N(g["sigma"] ** 2, g["backends"], params_of(white_params(g), x[c])),
+                  g["r"])
     assert int(wm.pinfo.abs().sum()) == 0
     b = rng.standard_normal((C, wm.ldb)) * 1e-7
     wm.resid(torch.as_tensor(b, device=ctx.device))
