@@ -423,6 +423,27 @@ int gs_pta_record(gs_ctx* ctx, int n_chain, int n_param, const double* x, double
  */
 int gs_pta_record_block(gs_ctx* ctx, int n_chain, int n_param, const double* x, int n_rec, int64_t chain_stride,
                         int64_t row_off, double* const* slots, const int* slot_sel, double* xlast);
+/*
+ * Posterior summaries of a block of recorded states, accumulated on the device for every chain.
+ * Row r = x + r * row_stride is an (n_chain, n_param) row-major state (row_stride >= n_chain *
+ * n_param) and belongs to sweep `sweep + r` (+ the counter of gs_ctx_set_sweep_counter when one is
+ * attached, so one captured launch serves every replay).  Rows of a sweep below `burn` are
+ * skipped; for every other row and every (c, j), with v = x[r][c][j]:
+ *   d = v - mid[j]:  s1[c][j] += d,  s2[c][j] += d * d   (one thread per (c, j), rows in
+ *     ascending r onto the stored value: s1 is the sequential sum bit for bit; s2 may use an fma);
+ *   lo[j] <= v <= hi[j]:  counts[j][min((int)floor((v - lo[j]) * scale[j]), n_bins - 1)] += 1
+ *     (exactly subtract, multiply, floor; the caller sets scale[j] = n_bins / (hi[j] - lo[j]));
+ *   otherwise (NaN and +-inf included):  outside[j] += 1  (the value still enters s1 and s2).
+ * n_acc[0] grows by the number of rows accumulated.  lo, hi, scale, mid [n_param]; s1, s2
+ * [n_chain x n_param]; counts [n_param x n_bins]; outside [n_param]; n_acc [1].  The accumulators
+ * persist across calls (the caller zeroes them); all counts are integers, no floating-point
+ * atomics: every result is reproducible.  1 <= n_bins <= 256, n_rows >= 0, n_chain >= 0,
+ * n_param >= 1, n_rows * n_chain < 2^31.
+ */
+int gs_chain_summary(gs_ctx* ctx, int n_chain, int n_param, const double* x, int n_rows, int64_t row_stride,
+                     int64_t sweep, int64_t burn, int n_bins, const double* lo, const double* hi,
+                     const double* scale, const double* mid, double* s1, double* s2, int64_t* counts,
+                     int64_t* outside, int64_t* n_acc);
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate);

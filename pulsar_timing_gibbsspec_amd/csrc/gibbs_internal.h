@@ -222,6 +222,17 @@ int launch_pta_record_block(hipStream_t s, int n_chain, int n_param, const doubl
                             int64_t chain_stride, int64_t row_off, double* const* slots, const int* slot_sel,
                             double* xlast);
 int launch_pta_gate_phiinv(hipStream_t s, const PtaGateArgs& a);
+
+struct SummaryArgs {  // gs_chain_summary (gibbs_summary.hip)
+  int n_chain, n_param, n_rows, n_bins;
+  int strip;  // chains per workgroup (set by the launcher)
+  int64_t row_stride, sweep, burn;
+  const int64_t* sweep_dev;  // ctx sweep counter (graph replay) or NULL
+  const double *x, *lo, *hi, *scale, *mid;
+  double *s1, *s2;
+  int64_t *counts, *outside, *n_acc;
+};
+int launch_chain_summary(hipStream_t s, SummaryArgs a);
 int launch_phi_powerlaw(hipStream_t s, int n_psr, int n_chain, int n_f, const double* x, int ldx,
                         const int32_t* pl_col, const double* lnphi, double* out);
 

@@ -107,6 +107,75 @@ def ess(chain, c=5.0):
     return np.array([chain.shape[0] / max(iat(chain[:, k], c), 1.0) for k in range(chain.shape[1])])
 
 
+def summarize_chains(X, lo, hi, n_bins):
+    """Host restatement of the on-device summary (engine.ChainSummary, sample(history="summary"))
+    for X (chains, n, k) -- e.g. a chains.npy -- with per-column ranges lo, hi (k,).  Sums are
+    accumulated in numpy long double about mid = (lo + hi) / 2:
+      s1_c = sum_i (X_ci - mid), s2_c = sum_i (X_ci - mid)^2,
+      m_c = mid + s1_c / n, v_c = (s2_c - s1_c^2 / n) / (n - 1),
+      mean = mean_c(m_c), W = mean_c(v_c), Bn = var_c(m_c, ddof=1),
+      var = sum_c s2_c / (C n) - (sum_c s1_c / (C n))^2  (pooled, ddof=0),
+      rhat = sqrt(((n - 1) / n W + Bn) / W), NaN where n < 2, C < 2 or W = 0.
+    counts (k, n_bins): a value v with lo <= v <= hi falls in bin min(floor((v - lo) * scale),
+    n_bins - 1), scale = n_bins / (hi - lo), all in double; anything else (NaN, +-inf) counts in
+    ``outside`` (k,) and still enters the sums.  Returns a dict of double / int64 arrays."""
+    X = np.asarray(X, float)
+    C, n, k = X.shape
+    n_bins = int(n_bins)
+    lo, hi = np.asarray(lo, float).reshape(k), np.asarray(hi, float).reshape(k)
+    scale = n_bins / (hi - lo)
+    L = np.longdouble
+    mid = (lo + hi) / 2
+    d = X.astype(L) - mid.astype(L)
+    s1, s2 = d.sum(axis=1), (d * d).sum(axis=1)                            # (C, k)
+    nan = np.full(k, np.nan)
+    with np.errstate(all="ignore"):
+        m_c = mid.astype(L) + s1 / L(n) if n else np.full((C, k), np.nan, L)
+        v_c = (s2 - s1 * s1 / L(n)) / L(n - 1) if n > 1 else np.full((C, k), np.nan, L)
+        mean, W = m_c.mean(axis=0), v_c.mean(axis=0)
+        Bn = m_c.var(axis=0, ddof=1) if C > 1 else nan.astype(L)
+        var = s2.sum(axis=0) / L(C * n) - (s1.sum(axis=0) / L(C * n)) ** 2 if n else nan.astype(L)
+        rhat = np.sqrt((L(n - 1) / L(n) * W + Bn) / W) if n > 1 else nan.astype(L)
+        rhat = np.where(W > 0, rhat, np.nan)
+    counts = np.zeros((k, n_bins), np.int64)
+    outside = np.zeros(k, np.int64)
+    for j in range(k):
+        v = X[:, :, j].ravel()
+        with np.errstate(invalid="ignore"):
+            inside = (v >= lo[j]) & (v <= hi[j])
+        b = np.minimum(np.floor((v[inside] - lo[j]) * scale[j]).astype(np.int64), n_bins - 1)
+        counts[j] = np.bincount(b, minlength=n_bins)
+        outside[j] = v.size - int(inside.sum())
+    f = lambda a: np.asarray(a, float)  # noqa: E731
+    return dict(counts=counts, outside=outside, n=np.int64(n), mean=f(mean), var=f(var), W=f(W), Bn=f(Bn),
+                rhat=f(rhat))
+
+
+def hist_quantiles(counts, lo, hi, q):
+    """Quantile(s) q of histograms counts (k, n_bins) over [lo, hi] (k,), e.g. a summary.npz's: linear
+    interpolation inside the bin where the cumulative count crosses q x total (the first non-empty
+    bin whose cumulative count reaches it).  Returns (k,) for a scalar q, (k, len(q)) otherwise; NaN
+    for an empty histogram."""
+    counts = np.atleast_2d(np.asarray(counts, float))
+    k, nb = counts.shape
+    lo, hi = np.broadcast_to(np.asarray(lo, float), (k,)), np.broadcast_to(np.asarray(hi, float), (k,))
+    qs = np.atleast_1d(np.asarray(q, float))
+    out = np.full((k, qs.size), np.nan)
+    for j in range(k):
+        cum = np.cumsum(counts[j])
+        if cum[-1] <= 0:
+            continue
+        for i, qq in enumerate(qs):
+            target = qq * cum[-1]
+            b = int(np.searchsorted(cum, target, side="left"))
+            b = min(b, nb - 1)
+            while counts[j, b] == 0:           # an empty bin holds no quantile: the next filled one
+                b += 1
+            below = cum[b] - counts[j, b]
+            out[j, i] = lo[j] + (b + (target - below) / counts[j, b]) * (hi[j] - lo[j]) / nb
+    return out[:, 0] if np.ndim(q) == 0 else out
+
+
 def acor(x, maxlag=10):
     """(tau, mean, sigma) of a 1-d chain: restatement of J. Goodman's ``acor``
     algorithm (PyPI ``acor`` 1.1.x, the module pulsar_gibbs.py:370-371 calls; absent

@@ -436,6 +436,96 @@ class BlockRecorder:
             (row or 0) * self.n_param, ptr(self.slots), ptr(self.sel), ptr(eng.xlast)), "gs_pta_record_block")
 
 
+class ChainSummary:
+    """Posterior summaries of every chain, accumulated on the device (gs_chain_summary): per
+    (chain, parameter) the moments s1 = sum (v - mid), s2 = sum (v - mid)^2 with mid = (lo + hi) / 2,
+    per parameter a histogram of n_bins bins over [lo, hi] pooled over the chains (``outside``
+    counts what falls beyond, NaN and +-inf included), and the number of rows taken, ``n_acc``.
+    Sweeps below ``burn`` are skipped on the device.  ``accumulate(eng)`` is one launch on the
+    engine's current state -- a graph node inside PTAChains.capture; ``finalize()`` reduces over the
+    chains (mean, variance, Gelman-Rubin R-hat) with ordinary torch work on the context's stream."""
+
+    def __init__(self, ctx, n_chain, n_param, lo, hi, n_bins=64, burn=0):
+        self.ctx, self.n_chain, self.n_param = ctx, int(n_chain), int(n_param)
+        self.n_bins, self.burn = int(n_bins), int(burn)
+        if not 1 <= self.n_bins <= 256:
+            raise ValueError(f"n_bins must be in 1..256 (got {n_bins})")
+        lo, hi = np.asarray(lo, float).ravel(), np.asarray(hi, float).ravel()
+        if lo.shape != (self.n_param,) or hi.shape != (self.n_param,):
+            raise ValueError(f"lo and hi must hold {self.n_param} bounds each")
+        if not (hi > lo).all():
+            raise ValueError("every histogram range needs hi > lo")
+        dev = ctx.device
+        self.lo_host, self.hi_host = lo, hi
+        self.lo, self.hi = _t(lo, torch.float64, dev), _t(hi, torch.float64, dev)
+        self.scale = _t(self.n_bins / (hi - lo), torch.float64, dev)       # the kernel's bin = floor((v - lo) scale)
+        self.mid = _t((lo + hi) / 2, torch.float64, dev)
+        self.s1 = torch.zeros(self.n_chain, self.n_param, dtype=torch.float64, device=dev)
+        self.s2 = torch.zeros_like(self.s1)
+        self.counts = torch.zeros(self.n_param, self.n_bins, dtype=torch.int64, device=dev)
+        self.outside = torch.zeros(self.n_param, dtype=torch.int64, device=dev)
+        self.n_acc = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def accumulate(self, eng):
+        """Add the engine's current state x (the row of sweep eng.it) for every chain."""
+        if (eng.C, eng.n_param) != (self.n_chain, self.n_param):
+            raise ValueError(f"the summary holds {self.n_chain} chains of {self.n_param} parameters, the engine "
+                             f"{eng.C} of {eng.n_param}")
+        check(self.ctx.lib.gs_chain_summary(
+            self.ctx.handle, self.n_chain, self.n_param, ptr(eng.x), 1, self.n_chain * self.n_param, eng.it,
+            self.burn, self.n_bins, ptr(self.lo), ptr(self.hi), ptr(self.scale), ptr(self.mid), ptr(self.s1),
+            ptr(self.s2), ptr(self.counts), ptr(self.outside), ptr(self.n_acc)), "gs_chain_summary")
+
+    # the two buffers a HistoryStreamer carries for a summary: int64 words (as float64 bit
+    # patterns) [counts | outside | n_acc] and the reduced moments [mean, var, W, Bn, rhat]
+    @property
+    def extra_shapes(self):
+        return [(self.n_param * (self.n_bins + 1) + 1,), (5, self.n_param)]
+
+    def finalize(self):
+        """Device tensors reduced over the C chains, n = n_acc rows each: counts, outside, n,
+        mean = mean_c(m_c) with m_c = mid + s1_c / n, W = mean_c(v_c) with v_c = (s2_c - s1_c^2 / n) /
+        (n - 1), Bn = var_c(m_c, ddof=1), var = sum_c s2_c / (C n) - (sum_c s1_c / (C n))^2 (the pooled
+        variance) and rhat = sqrt(((n - 1) / n W + Bn) / W), NaN where n < 2, C < 2 or W = 0.  No
+        host synchronisation."""
+        C = self.n_chain
+        nan = float("nan")
+        with torch.cuda.stream(self.ctx.stream):
+            n = self.n_acc.to(torch.float64)                               # [1], stays on the device
+            m_c = self.mid + self.s1 / n
+            v_c = (self.s2 - self.s1 * self.s1 / n) / (n - 1)
+            mean, W = m_c.mean(0), v_c.mean(0)
+            Bn = m_c.var(0, unbiased=True) if C > 1 else torch.full_like(mean, nan)
+            var = self.s2.sum(0) / (C * n) - (self.s1.sum(0) / (C * n)) ** 2
+            rhat = torch.sqrt(((n - 1) / n * W + Bn) / W)
+            rhat = torch.where((W > 0) & (n >= 2), rhat, torch.full_like(rhat, nan))
+            return dict(counts=self.counts, outside=self.outside, n=self.n_acc, mean=mean, var=var, W=W, Bn=Bn,
+                        rhat=rhat)
+
+    def pack(self, ints, reals):
+        """finalize() into two float64 buffers of ``extra_shapes`` (a streamer slot's)."""
+        f = self.finalize()
+        with torch.cuda.stream(self.ctx.stream):
+            w = ints.view(torch.int64)
+            nb = self.n_param * self.n_bins
+            w[:nb].copy_(f["counts"].view(-1))
+            w[nb:nb + self.n_param].copy_(f["outside"])
+            w[-1:].copy_(f["n"])
+            for i, k in enumerate(("mean", "var", "W", "Bn", "rhat")):
+                reals[i].copy_(f[k])
+
+    def unpack(self, ints, reals):
+        """Host arrays of what ``pack`` wrote (ints, reals: the fetched host tensors)."""
+        w = ints.numpy().view(np.int64)
+        nb = self.n_param * self.n_bins
+        out = dict(counts=w[:nb].reshape(self.n_param, self.n_bins).copy(),
+                   outside=w[nb:nb + self.n_param].copy(), n=np.int64(w[-1]))
+        r = reals.numpy()
+        for i, k in enumerate(("mean", "var", "W", "Bn", "rhat")):
+            out[k] = r[i].copy()
+        return out
+
+
 def grid3(rhomin, rhomax, n=1000, device="cuda"):
     """[rho_g | log rho_g | 0.5 log10 rho_g], rho_g = 10**linspace(log10 rhomin, log10 rhomax, n)
     — numpy on the host, so the device sees the reference's exact grid
@@ -635,17 +725,23 @@ class PTAChains:
         h.steps(self.x, nsteps, self.it, self.chain_base, inj=inj, q_rec=q_rec)
         h.fresh = False
 
-    def sweep_begin(self, x_rec=None, z0=None, u_red=None, mh_inj=None, block_rec=None):
+    def sweep_begin(self, x_rec=None, z0=None, u_red=None, mh_inj=None, block_rec=None, summary=None):
         """Record, [first draw], [hyper MH], tau and the local red draws.  Returns the local
         exchange slab [P_local, 1 or 2, n_f, C] (None when not sharded).  block_rec
-        (BlockRecorder, kept row or None): record through gs_pta_record_block instead of x_rec."""
+        (BlockRecorder, kept row or None): record through gs_pta_record_block instead of x_rec.
+        summary (ChainSummary): accumulates the recorded row (the state before this sweep) right
+        after the record call."""
         lib, h, m = self.ctx.lib, self.ctx.handle, self.model
         ii = self.it
+        if summary is not None and self.sharded:
+            raise NotImplementedError("a ChainSummary on a pulsar- or chain-sharded engine is not wired")
         if block_rec is not None:
             block_rec[0].record(self, block_rec[1])
         else:
             check(lib.gs_pta_record(h, self.C, self.n_param, ptr(self.x), ptr(x_rec), ptr(self.xlast)),
                   "gs_pta_record")
+        if summary is not None:
+            summary.accumulate(self)
         if ii == 0 or self.redraw_b:                           # pta_gibbs.py:669-670
             if self.hyper_pl or self.red_cond:
                 self._update_irn()
@@ -742,7 +838,7 @@ class PTAChains:
             raise RuntimeError("curn_mode='sum': a tau fell outside the fixed-point window (negative, "
                                "non-finite or >= rhomin_gw * 2**80); rerun with curn_mode='exact'")
 
-    def capture(self, n_sweeps, recorder=None):
+    def capture(self, n_sweeps, recorder=None, summary=None):
         """Capture n_sweeps steady-state sweeps (device Philox) into a hipGraph
         (torch.cuda.CUDAGraph around the C-ABI launches on the context's stream).
 
@@ -752,7 +848,9 @@ class PTAChains:
         eager sweeps.  The graph records x into ``graph_rec`` (n_sweeps, C, n_param), or, with a
         ``recorder`` (BlockRecorder), chain-major into the recorder's slot that its device flag
         selects at replay (sweep ii of the block -> the recorder's row for it, or xlast alone
-        where the recorder thins it out); there is no ``graph_rec`` then.
+        where the recorder thins it out); there is no ``graph_rec`` then.  A ``summary``
+        (ChainSummary) accumulates every captured sweep's row as a node of the graph (its burn-in
+        test reads the device sweep counter, so the one graph serves every replay).
 
         A pulsar-sharded engine captures its per-sweep exchange too: the RCCL all-reduce of
         the fixed-point tau-sum digits (or the [tau | x_red] all-gather) is issued on the
@@ -761,6 +859,8 @@ class PTAChains:
         the host and cannot be captured."""
         if self.it == 0:
             raise ValueError("run sweep 0 eagerly first (it draws b from x0, pta_gibbs.py:669-670)")
+        if summary is not None and self.sharded:
+            raise NotImplementedError("a ChainSummary on a pulsar- or chain-sharded engine is not wired")
         if self.sharded:
             import torch.distributed as dist
             if not dist.is_initialized() or dist.get_backend() != "nccl":
@@ -785,9 +885,9 @@ class PTAChains:
             with torch.cuda.graph(self.graph, stream=cap):
                 for i in range(n):
                     if recorder is None:
-                        self.sweep(x_rec=self.graph_rec[i])
+                        self.sweep(x_rec=self.graph_rec[i], summary=summary)
                     else:
-                        self.sweep(block_rec=(recorder, recorder.row_of(self._gbase, self.it)))
+                        self.sweep(block_rec=(recorder, recorder.row_of(self._gbase, self.it)), summary=summary)
                 check(lib.gs_counter_add(h, ptr(self._gcount), n), "gs_counter_add")
         finally:
             check(lib.gs_ctx_set_sweep_counter(h, None), "gs_ctx_set_sweep_counter")
@@ -808,14 +908,17 @@ class PTAChains:
             self.hyper.steps_total += self._g_hsteps
         return self.graph_rec
 
-    def sweep(self, x_rec=None, z0=None, z=None, u_red=None, u_curn=None, mh_inj=None, block_rec=None):
+    def sweep(self, x_rec=None, z0=None, z=None, u_red=None, u_curn=None, mh_inj=None, block_rec=None,
+              summary=None):
         """One PTABlockGibbs sweep for every chain; x_rec: (n_chain, n_param) row or None;
-        block_rec: (BlockRecorder, row in the block or None) records chain-major instead.
+        block_rec: (BlockRecorder, row in the block or None) records chain-major instead;
+        summary (ChainSummary): accumulates the recorded row on the device.
         z0/z: (P*n_chain, ldb) injected normals (original column order); u_red
         (n_chain, P, n_f) and u_curn (n_chain, n_f): injected uniforms; mh_inj (steps, n_chain,
         4): injected hyper-MH draws (scale, j, randn, rand)."""
         with fail_counts(self.ctx, self.fail_count):
-            slab = self.sweep_begin(x_rec=x_rec, z0=z0, u_red=u_red, mh_inj=mh_inj, block_rec=block_rec)
+            slab = self.sweep_begin(x_rec=x_rec, z0=z0, u_red=u_red, mh_inj=mh_inj, block_rec=block_rec,
+                                    summary=summary)
             if self.sharded:
                 # the collective is ordered after the slab's kernels: torch issues it against the
                 # CURRENT stream, which is made the context's (the kernels' stream; a no-op when the

@@ -56,6 +56,17 @@ def uniform_bounds(param):
     return float(m.group(1)), float(m.group(2))
 
 
+def flat_bounds(params):
+    """(lo, hi) arrays of every flat parameter's prior bounds, in ``expand_names`` order: a vector
+    parameter repeats its (pmin, pmax) for each of its elements."""
+    lo, hi = [], []
+    for p in params:
+        a, b = uniform_bounds(p)
+        lo.extend([a] * (p.size or 1))
+        hi.extend([b] * (p.size or 1))
+    return np.array(lo, float), np.array(hi, float)
+
+
 def power_bounds(param):
     """Free-spectrum power bounds rho = 10**(2 log10_rho) at the prior edges."""
     lo, hi = uniform_bounds(param)

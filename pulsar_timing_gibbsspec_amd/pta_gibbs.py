@@ -28,7 +28,8 @@ import torch
 
 from . import _lib
 from .engine import DeviceModel, PTAChains
-from .plumbing import basis_layout, expand_names, last_match, matching_indices, power_bounds, vector_to_dict
+from .plumbing import (basis_layout, expand_names, flat_bounds, last_match, matching_indices, power_bounds,
+                       vector_to_dict)
 from .pta_hyper import HYPER_WARMUP, HyperSpec, hyper_aclength
 from .pulsar_gibbs import HOST_CHAIN, resolve_seed
 
@@ -303,7 +304,7 @@ class PTABlockGibbs(object):
 
     # ------------------------------------------------------------ loop
     def sample(self, xs, outdir="./", niter=10000, resume=False, save_every=100, *, flush_final=False,
-               history="memory", record_chains=None, thin=1, slots="host"):
+               history="memory", record_chains=None, thin=1, slots="host", bins=64, burn=0):
         """PTABlockGibbs.sample (pta_gibbs.py:631-713): chain row ii = state before sweep ii;
         chain.txt (chain 0) rewritten with rows [:ii+1] at ii % 100 == 0, ii > 0;
         with nchains > 1 also chains.npy (leading chain axis).  flush_final=True also
@@ -325,9 +326,37 @@ class PTABlockGibbs(object):
         those of the default mode.  ``self.chain`` (returned) is chain 0's kept rows,
         (ceil(niter / t), npar).  Host memory does not grow with nchains x niter: two pinned slots
         of K x save_every / t x npar doubles, two pinned copies of the save-point state (x, b),
-        chain 0's history and one block's text."""
-        if history not in ("memory", "disk"):
-            raise ValueError("history must be 'memory' or 'disk'")
+        chain 0's history and one block's text.
+
+        history="summary": the history="disk" path with record_chains defaulting to 1 (chain 0, as
+        the reference keeps) and the posterior of EVERY chain accumulated on the device inside the
+        captured sweeps (engine.ChainSummary, gs_chain_summary): per parameter a histogram of
+        ``bins`` bins (1..256) over its prior range (plumbing.flat_bounds), mean, pooled variance and
+        the Gelman-Rubin W, Bn and R-hat across the chains, over every sweep ii >= ``burn``
+        (0..niter-1; thin affects the files only).  chain.txt, chains.npy, gibbs_state.npz and the
+        returned chain are those of history="disk" with the same record_chains and thin.
+        summary.npz (about npar x bins x 8 bytes) is rewritten at every save point -- then covering
+        rows [burn, last] -- and when sample() returns, covering [burn, niter-1]: names, lo, hi,
+        n_bins, burn, nchains, rows (sweeps run), n (rows accumulated per chain), counts (npar, bins)
+        and outside (npar,) int64, mean, var, W, Bn, rhat (npar,); ``self.summary`` holds the last one
+        (diagnostics.hist_quantiles reads medians and upper limits off counts;
+        diagnostics.summarize_chains restates every quantity for a host array).  The reduced arrays
+        of a save point travel with the recorder's slot and are fetched one block behind, like
+        (x, b).  resume=True is not wired for this mode."""
+        if history not in ("memory", "disk", "summary"):
+            raise ValueError("history must be 'memory', 'disk' or 'summary'")
+        if history != "summary" and (bins != 64 or burn != 0):
+            raise ValueError("bins and burn need history='summary'")
+        if history == "summary":
+            for name, v, a, b in (("bins", bins, 1, 256), ("burn", burn, 0, int(niter) - 1)):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not a <= v <= b:
+                    raise ValueError(f"{name} must be an integer in {a}..{b} (got {v!r})")
+            if resume:
+                raise NotImplementedError("resume=True is not wired for history='summary' (the accumulators are "
+                                          "not saved)")
+            return self._sample_disk(xs, outdir, int(niter), False, int(save_every), flush_final,
+                                     1 if record_chains is None else record_chains, thin, slots,
+                                     summary=(int(bins), int(burn)))
         if history == "disk":
             return self._sample_disk(xs, outdir, int(niter), resume, int(save_every), flush_final,
                                      record_chains, thin, slots)
@@ -420,11 +449,20 @@ class PTABlockGibbs(object):
             self.hyper_acceptance = eng.hyper.acceptance()
         return self.chain
 
-    def _sample_disk(self, xs, outdir, niter, resume, save_every, flush_final, record_chains, thin, slots):
+    def _write_summary(self, outdir, summary):
+        """summary.npz: written under a temporary name, then moved into place."""
+        tmp = f"{outdir}/summary.npz.tmp"
+        with open(tmp, "wb") as f:
+            np.savez(f, **summary)
+        os.replace(tmp, f"{outdir}/summary.npz")
+
+    def _sample_disk(self, xs, outdir, niter, resume, save_every, flush_final, record_chains, thin, slots,
+                     summary=None):
         """sample(history="disk"): see sample.  Blocks are the default mode's -- sweep 0, then
-        (k S, (k + 1) S] for S = save_every, then the rest -- so save points and rows agree."""
+        (k S, (k + 1) S] for S = save_every, then the rest -- so save points and rows agree.
+        summary = (bins, burn): history="summary"."""
         from .chain_writer import ChainWriter
-        from .engine import BlockRecorder
+        from .engine import BlockRecorder, ChainSummary
         nc, npar, S = self.nchains, len(xs), save_every
         K = nc if record_chains is None else record_chains
         for name, v in (("record_chains", K), ("thin", thin)):
@@ -473,8 +511,16 @@ class PTABlockGibbs(object):
         dev = self.ctx.device
         # per block and slot: the chain-major rows, the state of a save point (x, b) and
         # [fx overflow flag, failed b draws so far]
+        summ = None
+        if summary is not None:
+            # every chain's posterior accumulated by the sweeps themselves; a block that ends at a
+            # save point (or ends the run) carries the reduced arrays in two more buffers of its slot
+            lo, hi = flat_bounds(self.params)
+            summ = ChainSummary(self.ctx, nc, npar, lo, hi, n_bins=summary[0], burn=summary[1])
+            self.summary = None
         rec = BlockRecorder(self.ctx, K, S // t, npar, thin=t, direct=slots == "host",
-                            extra=[tuple(eng.x.shape), tuple(eng.b.shape), (2,)])
+                            extra=[tuple(eng.x.shape), tuple(eng.b.shape), (2,)]
+                            + (summ.extra_shapes if summ is not None else []))
         st = rec.streamer
         tstart = time.time()
         ii = start
@@ -497,7 +543,7 @@ class PTABlockGibbs(object):
             """Fetch a launched block (waits for that block only), check it, file it."""
             nonlocal seen_fail
             slot, i0, i1, save = blk
-            rows, x_h, b_h, flags = st.fetch(slot)
+            rows, x_h, b_h, flags, *sum_h = st.fetch(slot)
             eng.check_fx(ovf=int(flags[0]))        # curn_mode='sum': tau inside the fixed-point window
             nfail = int(flags[1])                  # failed (non-PD) b draws, b kept
             if nfail > seen_fail:
@@ -520,6 +566,12 @@ class PTABlockGibbs(object):
                 writer.append(rows, state=dict(rows=i1, x=x_h.numpy(), b=b_h.numpy(), **extra))
             elif last == 0:
                 writer.append(rows, commit=False)  # row 0 is filed with the first save point
+            if summ is not None and (save or i1 == niter):
+                # rows [burn, last] of every chain, reduced on the device behind the block
+                self.summary = dict(names=np.array(self.param_names), lo=summ.lo_host, hi=summ.hi_host,
+                                    n_bins=np.int64(summ.n_bins), burn=np.int64(summ.burn), nchains=np.int64(nc),
+                                    rows=np.int64(i1), **summ.unpack(*sum_h))
+                self._write_summary(outdir, self.summary)
 
         pending = None
         slot = 0
@@ -532,19 +584,21 @@ class PTABlockGibbs(object):
                 if pending is not None:            # nothing in flight while the graph is captured
                     drain(pending)
                     pending = None
-                eng.capture(S, recorder=rec)
+                eng.capture(S, recorder=rec, summary=summ)
                 captured = True
             rec.select(slot)
             if whole:
                 eng.replay()
             else:
                 for _ in range(nxt - ii):
-                    eng.sweep(block_rec=(rec, rec.row_of(ii, eng.it)))
+                    eng.sweep(block_rec=(rec, rec.row_of(ii, eng.it)), summary=summ)
             with torch.cuda.stream(eng.ctx.stream):
-                _, x_d, b_d, fl_d = st.buffers(slot)
+                _, x_d, b_d, fl_d, *sum_d = st.buffers(slot)
                 if save:
                     x_d.copy_(eng.x)
                     b_d.copy_(eng.b)
+                if summ is not None and (save or nxt == niter):
+                    summ.pack(*sum_d)
                 fl_d[0:1].copy_(eng.fx_ovf)
                 fl_d[1:2].copy_(eng.fail_count.sum(dtype=torch.float64).view(1))
             st.submit(slot)

@@ -10,6 +10,8 @@ Runs (each a fresh PTABlockGibbs on one synthetic.array_pta(kind, n_psr) model):
                   rewritten at every save point)
   diskK[-device]  sample(history="disk", record_chains=K or all): graph replays, block record
                   into pinned host slots (or HBM slots copied by a side stream: -device)
+  summaryK        sample(history="summary", record_chains=K): the disk path keeping K chains, plus
+                  every chain's posterior summary accumulated on the device (summary.npz)
 
 Timing: wall clock between the save points sample() reports ("Finished ... percent"), i.e. whole
 blocks of save_every sweeps with their recording and file work.  The first block (sweep 0, graph
@@ -124,6 +126,9 @@ def main():
                 k = None if spec == "all" else int(spec)
                 t, wall = run_sample(gb, x0, a.niter, a.save_every, outdir, history="disk", record_chains=k,
                                      slots=dest or "host")
+            elif name.startswith("summary"):
+                t, wall = run_sample(gb, x0, a.niter, a.save_every, outdir, history="summary",
+                                     record_chains=int(name[7:] or 1))
             else:
                 sys.exit(f"unknown run {name!r}")
             files = sum(os.path.getsize(os.path.join(outdir, f)) for f in os.listdir(outdir)) \
