@@ -105,9 +105,13 @@ enum {
   GS_OPT_DEBUG_HANDOFF = 8, /* test only: 1 = workgroup 0's first trio never publishes its first
                          hand-off (and the wait is shortened), so the 13th chain of workgroup 0
                          must end with info = -1 */
-  GS_OPT_LAST_SWEEP_SHAPE = 9 /* read only (gs_ctx_get_option): the workgroup shape the context's
+  GS_OPT_LAST_SWEEP_SHAPE = 9, /* read only (gs_ctx_get_option): the workgroup shape the context's
                          last gs_sweep_freespec or gs_bdraw_tiled launch ran -- 1 = 12-wave
                          hand-off, 2 = one chain per wave, 3 = two chains per wave, 0 = none yet */
+  GS_OPT_LAST_BDRAW_PERSIST = 10 /* read only (gs_ctx_get_option): the number of persistent
+                         workgroups of the context's last gs_bdraw_tiled launch (each drawing a
+                         contiguous range of chain groups), 0 = the classic grid of one workgroup
+                         per pulsar and chain-group block, or none yet */
 };
 
 typedef struct gs_ctx gs_ctx;

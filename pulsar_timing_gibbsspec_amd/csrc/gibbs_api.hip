@@ -19,6 +19,7 @@ struct gs_ctx {
   int sweep_sched = 0;    // GS_OPT_SWEEP_SCHED
   int dbg_handoff = 0;    // GS_OPT_DEBUG_HANDOFF
   int last_shape = 0;     // GS_OPT_LAST_SWEEP_SHAPE (read only)
+  int last_persist = 0;   // GS_OPT_LAST_BDRAW_PERSIST (read only)
   const int64_t* sweep_dev = nullptr;  // gs_ctx_set_sweep_counter
   int32_t* fail_counts = nullptr;      // gs_ctx_set_fail_counts
   int32_t* grid_fallback = nullptr;    // gs_ctx_set_grid_fallback_counter
@@ -289,6 +290,8 @@ int gs_ctx_set_option(gs_ctx* ctx, int option, int value) {
       return 0;
     case GS_OPT_LAST_SWEEP_SHAPE:
       return fail_arg(2, "GS_OPT_LAST_SWEEP_SHAPE is read only");
+    case GS_OPT_LAST_BDRAW_PERSIST:
+      return fail_arg(2, "GS_OPT_LAST_BDRAW_PERSIST is read only");
     default:
       return fail_arg(2, "unknown option");
   }
@@ -305,6 +308,7 @@ int gs_ctx_get_option(gs_ctx* ctx, int option) {
   if (option == GS_OPT_SWEEP_SCHED) return ctx->sweep_sched;
   if (option == GS_OPT_DEBUG_HANDOFF) return ctx->dbg_handoff;
   if (option == GS_OPT_LAST_SWEEP_SHAPE) return ctx->last_shape;
+  if (option == GS_OPT_LAST_BDRAW_PERSIST) return ctx->last_persist;
   return -1;
 }
 
@@ -514,7 +518,7 @@ int gs_bdraw_tiled(gs_ctx* ctx, int n_psr, int n_chain, int NF, int NMX, int ldb
   a.mask_per_sys = ctx->x_per_sys;
   a.phi_per_chain = ctx->phi_per_chain;
   a.sched = ctx->sweep_sched;
-  return launch_rc(launch_bdraw_tiled(ctx->stream, a, &ctx->last_shape), "k_bdraw_tiled");
+  return launch_rc(launch_bdraw_tiled(ctx->stream, a, &ctx->last_shape, &ctx->last_persist), "k_bdraw_tiled");
 }
 
 int gs_bdraw_sys(gs_ctx* ctx, int n_psr, int n_chain, int NF, int NMX, int ldb, const double* model,

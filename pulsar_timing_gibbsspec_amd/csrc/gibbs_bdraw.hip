@@ -1607,9 +1607,10 @@ static bool bdraw_pair_wins(const BdrawArgs& a) {
   if (a.sched || !GS_BDRAW_PAIR) return false;
   return (double)a.n_psr * (a.n_chain / 2) >= 8.0 * device_cus();
 }
-int launch_bdraw_tiled(hipStream_t s, const BdrawArgs& a0, int* shape) {
+int launch_bdraw_tiled(hipStream_t s, const BdrawArgs& a0, int* shape, int* persist) {
   constexpr int WPB = GS_BDRAW_WPB;
   BdrawArgs a = a0;
+  *persist = 0;
   if (bdraw_pair_wins(a)) {
     constexpr int PW = GS_PAIR_WPB;
     const size_t lds = ((size_t)a.mstride + (size_t)PW * GS_BPAIR_SCR) * sizeof(double);
@@ -1623,6 +1624,7 @@ int launch_bdraw_tiled(hipStream_t s, const BdrawArgs& a0, int* shape) {
         a.persist = per_cu * device_cus();
       hipLaunchKernelGGL(kern, dim3((unsigned)(a.persist ? a.persist : items)), dim3(64 * PW), lds, s, a);
       *shape = 3;
+      *persist = a.persist;
       return 0;
     }
   }
@@ -1640,6 +1642,7 @@ int launch_bdraw_tiled(hipStream_t s, const BdrawArgs& a0, int* shape) {
       a.persist = per_cu * device_cus();
     dim3 grid((unsigned)(a.persist ? a.persist : nwg));
     hipLaunchKernelGGL(kern, grid, dim3(64 * WPB), lds, s, a);
+    *persist = a.persist;
     return 0;
   };
   const bool fx = model_tiled_fix(a.NMX);

@@ -163,8 +163,9 @@ struct RhoArgs {
 // *shape: the workgroup shape launched (GS_OPT_LAST_SWEEP_SHAPE: 1 hand-off, 2 one chain per wave, 3 two)
 int launch_sweep_freespec(hipStream_t s, const SweepArgs& a, int* shape);
 int launch_bdraw(hipStream_t s, const BdrawArgs& a);
-// *shape: 2 one chain per wave (k_bdraw_tiled), 3 two chains per wave (k_bdraw_pair)
-int launch_bdraw_tiled(hipStream_t s, const BdrawArgs& a, int* shape);
+// *shape: 2 one chain per wave (k_bdraw_tiled), 3 two chains per wave (k_bdraw_pair); *persist: the
+// persistent workgroup count launched, 0 for the classic grid (GS_OPT_LAST_BDRAW_PERSIST)
+int launch_bdraw_tiled(hipStream_t s, const BdrawArgs& a, int* shape, int* persist);
 int launch_model_tile(hipStream_t s, const double* model, int n_psr, int NF, int NMX, const int32_t* nm,
                       double* tiled);
 // large free-spectrum blocks (64 < NF <= 255), tiles in a context-owned workspace
