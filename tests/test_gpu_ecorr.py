@@ -413,14 +413,21 @@ def test_ecorr_bdraw_chain_mask_mixed(ctx):
             assert np.all(B[c] == sentinel), c
 
 
+SCHUR_TILE_EDGES = [(15, 5, 0), (16, 33, 1), (31, 64, 0), (32, 65, 1), (47, 7, 0), (95, 137, 1), (96, 33, 0),
+                    (127, 64, 1)]
+
+
 @pytest.mark.parametrize("mR,ne,offset", [(60, 137, 0), (100, 137, 0), (120, 137, 0), (60, 1, 1), (76, 33, 1),
-                                           (100, 64, 1)])
+                                           (100, 64, 1)] + SCHUR_TILE_EDGES)
 def test_ecorr_schur_direct(ctx, mR, ne, offset):
     """gs_ecorr_schur through the C-ABI on random operands: TNT = A - B^T diag(1/a) B,
     d = dR - B^T (d_E / a), aux = (sum log a, sum d_E^2 / a, sum log phi_E, 0), against
     numpy.  mR = 100 / 120 use 7 / 8 tile columns, whose accumulators are split over two
     launches (one would need ~290 VGPRs).  offset = 1: Bx at an 8-byte offset address (the LDS-DMA
-    staging in 4-byte units); ne = 1 / 33 / 64: partial and exact 32-epoch chunks."""
+    staging in 4-byte units); ne = 1 / 33 / 64: partial and exact 32-epoch chunks.
+    SCHUR_TILE_EDGES: 1, 2, 3, 6, 7 tile columns and 8 at its largest mR, with mR + 1 filling the last
+    tile exactly (15, 31, 47, 95, 127) and d_E alone in a tile of its own (16, 32, 96) -- these against
+    the long-double tests/ecorr_ref.schur_ref."""
     import torch
     from pulsar_timing_gibbsspec_amd._lib import check, ptr
     rng = np.random.default_rng(mR + ne)
@@ -453,14 +460,19 @@ def test_ecorr_schur_direct(ctx, mR, ne, offset):
     TNT, d, aux = TNT.cpu().numpy(), d.cpu().numpy(), aux.cpu().numpy()
     B, dE = Bx[:, :mR], Bx[:, mR]
     for c in range(C):
-        ph = 10.0 ** (2.0 * x[c, xcol])
-        a = Dg + 1.0 / ph[ebk]
-        want = A - B.T @ (B / a[:, None])
+        if (mR, ne, offset) in SCHUR_TILE_EDGES:
+            from tests.ecorr_ref import schur_ref
+            want, wd, waux = (np.asarray(v, dtype=np.float64) for v in schur_ref(Bx, Dg, ebk, x[c], xcol, A, dR, mR))
+        else:
+            ph = 10.0 ** (2.0 * x[c, xcol])
+            a = Dg + 1.0 / ph[ebk]
+            want, wd = A - B.T @ (B / a[:, None]), dR - B.T @ (dE / a)
+            waux = [np.sum(np.log(a)), np.sum(dE ** 2 / a), np.sum(np.log(ph[ebk]))]
+        print(f"ECORR-SHAPES c.schur {np.max(np.abs(TNT[c] - want)) / np.max(np.abs(want)):.3e}")
         assert np.max(np.abs(TNT[c] - want)) <= 1e-12 * np.max(np.abs(want)), (mR, c)
         assert np.array_equal(TNT[c], TNT[c].T)
-        assert normwise_rel(d[c], dR - B.T @ (dE / a)) < 1e-12
-        np.testing.assert_allclose(aux[c, :3], [np.sum(np.log(a)), np.sum(dE ** 2 / a), np.sum(np.log(ph[ebk]))],
-                                   rtol=1e-12)
+        assert normwise_rel(d[c], wd) < 1e-12
+        np.testing.assert_allclose(aux[c, :3], waux[:3], rtol=1e-12)
         assert aux[c, 3] == 0.0
 
 
