@@ -1158,8 +1158,8 @@ __global__ __launch_bounds__(64 * WPB, GS_MINW(BC, NFC, NTC)) void k_sweep_frees
 // bit: the Philox counters are per chain, a chain whose gate is shut has its (computed) draw discarded
 // exactly where the one-chain kernel skips it, and a failed factorisation keeps that chain's b.
 // 2 waves per SIMD (both chains' tiles: ~200 VGPRs): 4096 chains are 2048 waves, one round.
-// per wave: 2 scratches, b save, z_M, x park
-constexpr int GS_PAIR_SCR = 2 * gs_tile_scr(60) + 256 + 128 + 128;
+// per wave: 2 scratches, b save, z_M, x park, the next draw's normals (PairPrefetch's slot)
+constexpr int GS_PAIR_SCR = 2 * gs_tile_scr(60) + 256 + 128 + 128 + 160;
 // GS_PAIR_WPB: waves (chain pairs) per workgroup
 #ifndef GS_PAIR_WPB
 #define GS_PAIR_WPB 4
@@ -1196,6 +1196,10 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
   double* bsave = wl + 2 * gs_tile_scr(60);  // [2][128]: the chains' previous b (failed or shut draws)
   double* zmslot = bsave + 256;              // [2][64]: the chains' z_M during the draw
   double* xpark = zmslot + 128;              // [2][64]: the chains' x during the draw (not in VGPRs)
+  double* pfslot = xpark + 128;              // [2][80]: the next draw's normals, written in this draw's tail
+  // the slot holds the normals of the draw that comes next (wave-uniform).  Not at a launch's first draw,
+  // nor after a sweep whose draw was skipped (both gates shut): those generate their normals inline
+  bool pfv = false;
 
   const double irhomin = 1.0 / A.rhomin, irhomax = 1.0 / A.rhomax;
   const int64_t xr_step = n_sys * NFR;
@@ -1255,7 +1259,12 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
           const double ta = gtile::bcast_lane_bp(tau2[0], src), tb = gtile::bcast_lane_bp(tau2[1], src);
           const double tau = h ? tb : ta;
           double U, u2;
-          gs_uniform2(gs_counter(k, ii, h ? gchain[1] : gchain[0], p + A.psr_base, GS_EV_RHO), A.key, U, u2);
+          // (kc opaque: the first Philox round's products of the lane, invariant over the sweeps, were
+          // hoisted out of the sweep loop, spilled across the draw and reloaded here)
+          int kc = k;
+          uint32_t cz = (uint32_t)(h ? gchain[1] : gchain[0]);  // the counter's chain word
+          asm volatile("" : "+v"(kc), "+v"(cz));
+          gs_uniform2(gs_counter(kc, ii, cz, p + A.psr_base, GS_EV_RHO), pair_key(A.key), U, u2);
           // (1 - exp(arg) is exactly 1 where the law skips the exp, so its one ballot over both chains
           // draws the same values as a ballot per chain)
           const RhoDraw rd = rho_given_b(tau, U, A.rhomin, A.rhomax, irhomin, irhomax, am);
@@ -1275,13 +1284,23 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
           }
         }
         if constexpr (GS_PAIR_RHO_PRIO > 0) __builtin_amdgcn_s_setprio(GS_BASE_PRIO);
-        if (!draw[0] && !draw[1]) break;
+        if (!draw[0] && !draw[1]) {
+          pfv = false;  // the slot's normals were this sweep's
+          break;
+        }
         ev = GS_EV_B;
       }
       double zF[2], zM[2];
+      if (pfv) {
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch) pair_prefetch_read(pfslot, ch, lane, zF[ch], zM[ch]);
+      } else {
+#pragma unroll
+        for (int ch = 0; ch < 2; ++ch)
+          gs_normal2(gs_counter(lane, ii, gchain[ch], p + A.psr_base, ev), pair_key(A.key), zF[ch], zM[ch]);
+      }
 #pragma unroll
       for (int ch = 0; ch < 2; ++ch) {
-        gs_normal2(gs_counter(lane, ii, gchain[ch], p + A.psr_base, ev), A.key, zF[ch], zM[ch]);
         if (pass == 0) phinv[ch] = act ? 1.0 / pow(10.0, 2.0 * x[ch]) : 0.0;  // first draw from xs
         // the previous b waits in the wave's save slot (a failed or shut draw keeps it)
         bsave[128 * ch + lane] = bF[ch];
@@ -1289,7 +1308,13 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
         xpark[64 * ch + lane] = x[ch];
       }
       int f[2];
-      bdraw_tile_pair60<true>(M, NMXe, nM, lane, phinv, zF, zM, bF, bM, scr, zmslot, f);
+      // the draw that follows is GS_EV_B of this sweep (after pass 0) or of the next: same counters,
+      // functions and bits as the inline path.  (The last sweep's prefetch is generated and dropped: a
+      // uniform branch around it would cut the draw's tail into separate scheduling regions.)
+      const PairPrefetch pf = {A.key, (uint32_t)(ii + pass), {(uint32_t)gchain[0], (uint32_t)gchain[1]},
+                               p + A.psr_base, GS_EV_B, pfslot};
+      bdraw_tile_pair60<true, true>(M, NMXe, nM, lane, phinv, zF, zM, bF, bM, scr, zmslot, f, pf);
+      pfv = true;
       gtile::lds_fence();
 #pragma unroll
       for (int ch = 0; ch < 2; ++ch) {
@@ -1529,7 +1554,8 @@ int launch_sweep_freespec(hipStream_t s, const SweepArgs& a, int* shape) {
   if (pair_ok && sweep_pair_wins(a)) {
     constexpr int WPB = GS_PAIR_WPB;
     const size_t lds = (mlds + (size_t)WPB * GS_PAIR_SCR) * sizeof(double);
-    if (lds <= device_lds_optin()) {
+    // two workgroups per CU (the kernel's 2 waves per SIMD) must fit the CU's 160 KB
+    if (lds <= device_lds_optin() && 2 * lds <= 160 * 1024) {
       const int nb = (a.n_chain + 2 * WPB - 1) / (2 * WPB);
       if (lds > 65536 && set_lds(k_sweep_pair<WPB>, lds)) return 2;
       hipLaunchKernelGGL((k_sweep_pair<WPB>), dim3((unsigned)(a.n_psr * nb)), dim3(64 * WPB), lds, s, a);

@@ -10,7 +10,8 @@
 // step and lane mask serve both chains (tile_elim_pair).  The layout is entered and left by
 // v_permlane32_swap (16 32-bit swaps each way per tile pair); the TRSM and trailing update run per
 // chain in the MFMA layout, their two instruction streams independent (ILP), and the solves and fixed
-// block of both chains interleaved step by step (shared LDS round trips and G / R loads).  Both chains'
+// block of both chains interleaved step by step (shared LDS round trips and G / R loads; the row-group
+// sums of both chains in registers, qsum2; the next draw's normals in the last steps' LDS waits).  Both chains'
 // 2 x 10 tiles fit 2 waves per SIMD (k_sweep_pair: 256 VGPRs, ~10 spilled outside the draw); measured in
 // tools/probe/pair_fact_probe.hip (r06j): the factorisation at 2 waves/SIMD 8,187 SIMD cycles per chain
 // against the one-chain kernel's 9,430 at its 3 waves/SIMD.
@@ -41,18 +42,87 @@ __host__ __device__ constexpr int ptk(int k) { return 2 * (k >> 2) + ((k >> 1) &
 #define GS_PAIR_FIX_PRIO 1
 #endif
 
-// gtile::to_row of two chains' column vectors through their own LDS rows, one round trip for both
-__device__ __forceinline__ void to_row2(const double (&v)[2], double* const (&vb)[2], gs_d4 (&o)[2], int q, int c) {
+// The Philox key for one use inside k_sweep_pair's sweep loop, opaque: the ten round keys are then
+// scalar adds at the use.  Taken straight from the kernel argument they were hoisted out of the sweep
+// loop, held in spilled SGPRs across the draw and brought back with a v_readlane_b32 each (VALU issue
+// slots) at every Philox site of every sweep.
+__device__ __forceinline__ gs_key pair_key(gs_key k) {
+  asm volatile("" : "+s"(k.k0), "+s"(k.k1));
+  return k;
+}
+
+// gtile::qsum of two chains' partial sums without LDS: v_permlane16_swap puts rows (0, 1) / (2, 3) of
+// p0 in rows 0 / 2 and those of p1 in rows 1 / 3 of the two operands, v_permlane32_swap brings the two
+// halves together.  Per lane the sum is still (p + p^16) + (...^32) with the operands of the commutative
+// adds in either order: the bits of gtile::qsum.  The result holds chain 0 in rows 0 and 2 and chain 1
+// in rows 1 and 3 (row = lane >> 4).
+__device__ __forceinline__ double qsum2(double p0, double p1) {
+  const unsigned long long ua = (unsigned long long)__double_as_longlong(p0);
+  const unsigned long long ub = (unsigned long long)__double_as_longlong(p1);
+  auto lo = __builtin_amdgcn_permlane16_swap((unsigned)ua, (unsigned)ub, false, false);
+  auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(ua >> 32), (unsigned)(ub >> 32), false, false);
+  const double s = __longlong_as_double((long long)(((unsigned long long)hi[0] << 32) | lo[0])) +
+                   __longlong_as_double((long long)(((unsigned long long)hi[1] << 32) | lo[1]));
+  double x = s, y = s;
+  gpair::swap32(x, y);  // x: the lower half's s in both halves, y: the upper half's
+  return x + y;
+}
+
+// gtile::to_row of two chains' column vectors in one LDS round trip.  v is in qsum2's layout (the lane's
+// row holds chain (lane >> 4) & 1): one store to the lane's chain's row vbh, then both chains' rows.
+// fill() (where fill_on): independent work of the caller's, placed between the loads' issue and their
+// first use.
+template <typename F>
+__device__ __forceinline__ void to_row2(double v, double* vbh, double* const (&vb)[2], gs_d4 (&o)[2], int q, int c,
+                                        bool fill_on, F&& fill) {
   gtile::lds_fence();
-  vb[0][c] = v[0];
-  vb[1][c] = v[1];
+  vbh[c] = v;  // the two lanes of column c of each chain write the same value
   gtile::lds_fence();
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     o[0][s] = vb[0][4 * s + q];
     o[1][s] = vb[1][4 * s + q];
   }
+  if (fill_on) {
+    __builtin_amdgcn_sched_barrier(0);
+    fill();
+    __builtin_amdgcn_sched_barrier(0);
+  }
   gtile::lds_fence();
+}
+
+// The next draw's normals of both chains, generated inside this draw's tail (bdraw_tile_pair60<PR, true>):
+// the Philox counters' sweep, chains, pulsar and event, and the wave's slot of 160 doubles (per chain
+// z_F of 64 lanes, then z_M of lanes 0..15 -- the tiled fixed block has nM <= 16).
+struct PairPrefetch {
+  gs_key key;
+  uint32_t sweep, chain[2];  // the counter's words (the low halves of the kernel's 64-bit indices)
+  int psr, event;
+  double* slot;
+};
+// gs_normal2 of chain ch in two slices, each placed in the wait of one LDS round trip of the solve:
+// the uniforms (Philox) ...
+__device__ __forceinline__ void pair_prefetch_uniforms(const PairPrefetch& pf, int ch, int lane, double& u1, double& u2) {
+  int ln = lane;
+  asm volatile("" : "+v"(ln));  // opaque: the first round's products of the lane are not hoisted out of the
+                                // sweep loop (and spilled across the draw)
+  gs_uniform2(gs_counter(ln, pf.sweep, pf.chain[ch], pf.psr, pf.event), pair_key(pf.key), u1, u2);
+}
+// ... and Box-Muller (gs_box_muller's operations) into the slot.  One store per value and no divergent
+// branch (the draw's tail stays one scheduling region): lanes >= 16 store their z_F a second time where
+// lanes < 16 store z_M.
+__device__ __forceinline__ void pair_prefetch_normals(const PairPrefetch& pf, int ch, int lane, double u1, double u2) {
+  double zF, zM;
+  gs_box_muller(u1, u2, zF, zM);
+  double* s = pf.slot + 80 * ch;
+  s[lane] = zF;
+  s[lane < 16 ? 64 + lane : lane] = lane < 16 ? zM : zF;
+}
+// ... and back: each lane reads what it stored itself, so no fence is needed in between
+__device__ __forceinline__ void pair_prefetch_read(const double* slot, int ch, int lane, double& zF, double& zM) {
+  const double* s = slot + 80 * ch;
+  zF = s[lane];
+  zM = s[64 + (lane & 15)];  // lanes >= nM (<= 16) of z_M are not used
 }
 
 // tile_elim1's column elimination on two chains at once (paired layout): on return B * rsd is U^-1 of
@@ -109,12 +179,13 @@ __device__ __forceinline__ void tile_elim_pair(double (&A)[8], double (&B)[8], d
 // CPC = 12 (NF = 60), LNL = 0, !WIDE, PR> for each, sharing the block's loads and the diagonal
 // eliminations.  scr[ch]: each chain's gs_tile_scr(60) doubles of the wave's LDS scratch; zmslot: 128
 // more (the chains' z_M, staged before the factorisation so they are not held in registers).  Returns each
-// chain's first failed pivot (0: the draw is valid) in fail[ch].
-template <bool PR>
+// chain's first failed pivot (0: the draw is valid) in fail[ch].  PF (k_sweep_pair): the normals of the
+// draw that follows, counters in pf, are generated inside the last two solve steps and left in pf.slot.
+template <bool PR, bool PF = false>
 __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, int nM, int lane, const double (&phinv)[2],
                                                   const double (&zF)[2], const double (&zM)[2], double (&bF)[2],
                                                   double (&bM)[2], double* const (&scr)[2], double* zmslot,
-                                                  int (&fail)[2]) {
+                                                  int (&fail)[2], const PairPrefetch& pf = PairPrefetch()) {
   using namespace gtile;
   constexpr int NT = 4, NF = 60, CP = 12, NTILE = NT * (NT + 1) / 2;
   const int q = lane >> 4, c = lane & 15;
@@ -264,11 +335,31 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
       ycol[ch][NT - 1] = ylast[ch];
     }
     if constexpr (PR && GS_SOLVE_PRIO > 0) __builtin_amdgcn_s_setprio(GS_SOLVE_PRIO);
-    double xcol[2][NT];
     gs_d4 xrow[2][NT];
+    double pu1 = 0.0, pu2 = 0.0;  // the prefetch's uniforms between its two slices
+    // the column vectors of both chains in qsum2's layout: the lane's row holds chain hs
+    // (hv opaque: a select on a lane-varying index of ycol[][] is turned into a private-array load)
+    int hv = q & 1;
+    asm volatile("" : "+v"(hv));
+    const bool hs = hv != 0;
+    double* const vbh = vb[0] + hv * (vb[1] - vb[0]);
+    double* const obh = vbh + (ob[0] - vb[0]);
+    double ycs[NT], xcol[NT];
+#pragma unroll
+    for (int K = 0; K < NT; ++K) ycs[K] = hs ? ycol[1][K] : ycol[0][K];
 #pragma unroll
     for (int K = NT - 1; K >= 0; --K) {
-      double v[2];
+      // the next draw's normals, one chain per step once row 2's tiles are dead (before that every
+      // VGPR is taken): dense VALU work placed in the waits of this step's two LDS round trips, the
+      // uniforms in the first and Box-Muller in the second
+      const bool pfk = PF && K < 2;
+      auto fill0 = [&]() {
+        if constexpr (PF) pair_prefetch_uniforms(pf, 1 - K, lane, pu1, pu2);
+      };
+      auto fill1 = [&]() {
+        if constexpr (PF) pair_prefetch_normals(pf, 1 - K, lane, pu1, pu2);
+      };
+      double pk[2];
 #pragma unroll
       for (int ch = 0; ch < 2; ++ch) {
         double p = 0.0;
@@ -278,30 +369,28 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
 #pragma unroll
           for (int s = 0; s < 4; ++s) p = fma(ut[s], xrow[ch][J][s], p);
         }
-        if (K + 1 < NT) p = qsum(p);
-        v[ch] = ycol[ch][K] + ob[ch][16 * K + c] - p;
+        pk[ch] = p;
       }
       gs_d4 sr[2];
-      to_row2(v, vb, sr, q, c);
+      const double pq = (K + 1 < NT) ? qsum2(pk[0], pk[1]) : 0.0;
+      to_row2(ycs[K] + obh[16 * K + c] - pq, vbh, vb, sr, q, c, pfk, fill0);
+      double p2[2];
 #pragma unroll
       for (int ch = 0; ch < 2; ++ch) {
         const gs_d4 W = t[ch][tix(K, K, NT)];
-        double p2 = 0.0;
+        p2[ch] = 0.0;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) p2 = fma(W[s], sr[ch][s], p2);
-        xcol[ch][K] = qsum(p2);
+        for (int s = 0; s < 4; ++s) p2[ch] = fma(W[s], sr[ch][s], p2[ch]);
       }
-      const double xv[2] = {xcol[0][K], xcol[1][K]};
       gs_d4 xr[2];
-      to_row2(xv, vb, xr, q, c);
+      xcol[K] = qsum2(p2[0], p2[1]);
+      to_row2(xcol[K], vbh, vb, xr, q, c, pfk, fill1);
       xrow[0][K] = xr[0];
       xrow[1][K] = xr[1];
     }
     lds_fence();
 #pragma unroll
-    for (int ch = 0; ch < 2; ++ch)
-#pragma unroll
-      for (int K = 0; K < NT; ++K) ob[ch][16 * K + c] = xcol[ch][K];
+    for (int K = 0; K < NT; ++K) obh[16 * K + c] = xcol[K];
     lds_fence();
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) bF[ch] = (lane < NF) ? ob[ch][lane] : 0.0;
@@ -331,11 +420,8 @@ __device__ __forceinline__ void bdraw_tile_pair60(const ModelTiled& M, int NMX, 
       p[1] = fma(r, zm[1][4 * s + q], p[1]);
     }
     const double hr = M.h[row + z0];
-#pragma unroll
-    for (int ch = 0; ch < 2; ++ch) {
-      const double pp = qsum(p[ch]);
-      ob[ch][row] = rok ? hr + pp : 0.0;
-    }
+    const double pp = qsum2(p[0], p[1]);
+    obh[row] = rok ? hr + pp : 0.0;
     lds_fence();
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) bM[ch] = (lane < nM) ? ob[ch][lane] : 0.0;
