@@ -67,6 +67,43 @@ __host__ __device__ inline int64_t model_tiled_doubles(int NF, int NMX) {
   return rm > fix ? rm : fix;
 }
 
+// Factorisation variants of the b draw (BdrawArgs / SweepArgs bcast, GS_OPT_BCAST) and the per-wave
+// LDS scratch (doubles) of each
+#define GS_BCAST_READLANE 0
+#define GS_BCAST_LDS 1
+#define GS_BCAST_BATCH 2
+#define GS_BCAST_TILE 3
+#define GS_SCR_DOUBLES(bc, nf) ((bc) == GS_BCAST_TILE ? gs_tile_scr(nf) : 64)
+
+// The dynamic LDS of a one-chain fused-sweep workgroup (k_sweep_freespec, k_sweep_freespec_rm) after
+// its model block, in doubles from the block's end: a scratch per wave (the variant BC's; a run-time NF
+// takes the tile variant) and a save slot per wave for the previous b (bF | bM).  The 12-wave hand-off
+// shape adds a park slot per wave for its own chain's state (x | bF | bM | fail), a hand-off slot of
+// the same form per trio of waves, and the trios' int progress flags.  Kernel, launcher and
+// gs_sweep_lds_bytes all read this one definition: a kernel that indexed past what its launcher asked
+// for would write into a neighbour's LDS.
+// The scratches come first (GS_SCR_DOUBLES each); where the other regions start, for WPB waves with
+// scratches of S doubles.  (Macros expanded at each pointer, not a struct filled once or functions: the
+// run-time-NF kernels' code is only unchanged if each offset is spelt out where it is used.)
+struct SweepLds {
+  static constexpr int SAVE = 128, STATE = 256, HANDOFF_WPB = 12, TRIOS = HANDOFF_WPB / 3;
+  static constexpr int HANDS = TRIOS * STATE;  // all the hand-off slots: the flags follow them
+};
+#define GS_SWEEP_LDS_SAVE(S, WPB) ((WPB) * (S))
+#define GS_SWEEP_LDS_PARK(S, WPB) ((WPB) * ((S) + SweepLds::SAVE))
+#define GS_SWEEP_LDS_HAND(S, WPB) ((WPB) * ((S) + SweepLds::SAVE + SweepLds::STATE))
+// GS_SWEEP_LDS_FLAGS: deliberately a bare sum of two terms, to be ADDED to a pointer or an offset only
+// (`lds + mlds + GS_SWEEP_LDS_FLAGS(..)`): the kernels add the terms to the pointer one by one, and as one
+// parenthesised int the run-time-NF hand-off kernels compile to other code.  Parenthesise it anywhere else.
+#define GS_SWEEP_LDS_FLAGS(S, WPB) GS_SWEEP_LDS_HAND(S, WPB) + SweepLds::HANDS
+#define GS_SWEEP_LDS_TOTAL(S, WPB)                              \
+  ((WPB) != SweepLds::HANDOFF_WPB ? GS_SWEEP_LDS_PARK(S, WPB) \
+                                  : (GS_SWEEP_LDS_FLAGS(S, WPB)) + (SweepLds::TRIOS * 4 + 7) / 8)
+// bytes of the whole workgroup's dynamic LDS, model block of mlds doubles included
+__host__ __device__ constexpr size_t sweep_lds_bytes(int64_t mlds, int NF, int BC, int WPB) {
+  return (size_t)(mlds + GS_SWEEP_LDS_TOTAL(GS_SCR_DOUBLES(BC, NF), WPB)) * sizeof(double);
+}
+
 // gs_prefix / gs_prefix_sys / gs_prefix_dd (gibbs_prefix.hip)
 struct PrefixArgs {
   int n_psr, n_chain, NF, NMX;
@@ -98,7 +135,7 @@ struct LnlArgs {
 };
 int launch_lnlike_marg(hipStream_t s, const LnlArgs& a);
 
-// PTA red-noise hyper-parameter Metropolis block (gs_hyper_mh, gibbs_bdraw.hip)
+// PTA red-noise hyper-parameter Metropolis block (gs_hyper_mh, gibbs_lnlike.hip)
 struct HyperMhArgs {
   int n_psr, n_chain, NF, NMX, ldx, n_h, nsteps, red_kind;
   int64_t mstride, sweep, chain_base;

@@ -389,7 +389,7 @@ __device__ __forceinline__ double add_on_diag(double v, double a, int s) {
 }  // namespace gtile
 
 // A pulsar's model block in the register-tile layout (gibbs_internal.h model_tiled_*), built
-// once per fused-sweep launch in LDS (gibbs_bdraw.hip stage_model_tiled): every tile element a
+// once per fused-sweep launch in LDS (gibbs_bdraw.h stage_model_tiled): every tile element a
 // lane needs sits at lane + 64 (4 tile + register), so the per-draw loads are lane-linear with
 // immediate offsets -- no per-element address arithmetic, no exec branches for the ragged edges,
 // no bank conflicts.  S: the augmented Schur block with dF on its first padding row/column and
@@ -414,7 +414,7 @@ struct model_is_tiled<ModelTiled> {
   static constexpr bool value = true;
 };
 
-// Model block view (see gibbs_bdraw.hip ModelLds): S0 NF x (NF+1), dF, G NMX x (NF+1),
+// Model block view (see gibbs_bdraw.h ModelLds): S0 NF x (NF+1), dF, G NMX x (NF+1),
 // h, R NMX x NMX.  Same interface and outputs as bdraw_wave.
 // LNL = true (the marginalised likelihood, gs_lnlike_marg): stop after the factorisation
 // and return, wave-uniform, bF = |y|^2 = dF^T S^-1 dF and bM = log det S (sum of the log
@@ -746,6 +746,18 @@ __device__ __forceinline__ int bdraw_tile_n(const ModelT& M, int NMX, int nM, in
                                             double zF, double zM, double& bF, double& bM,
                                             double* __restrict__ scr, int NF) {
   return bdraw_tile_core<NT, -1, LNL, false, PR>(M, NMX, nM, lane, phinv, zF, zM, bF, bM, scr, NF);
+}
+
+// The tile core of a kernel instantiated by dispatch_nf (gibbs_bdraw.h): NFC = NF > 0 fixed at compile
+// time, or NFC == 0 and NTC tile rows with NF at run time.
+template <int NFC, int NTC, int LNL, bool PR, typename ModelT>
+__device__ __forceinline__ int bdraw_tile_nf(const ModelT& M, int NMX, int nM, int lane, double phinv,
+                                             double zF, double zM, double& bF, double& bM, double* scr,
+                                             int NF) {
+  if constexpr (NFC == 0)
+    return bdraw_tile_n<NTC, LNL, PR>(M, NMX, nM, lane, phinv, zF, zM, bF, bM, scr, NF);
+  else
+    return bdraw_tile<NFC, LNL, PR>(M, NMX, nM, lane, phinv, zF, zM, bF, bM, scr);
 }
 
 // Same with up to 128 timing-model columns (see bdraw_tile_core, WIDE).

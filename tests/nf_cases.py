@@ -1,7 +1,7 @@
 """Shapes and shared references of the NF class x fixed-block layout tests
 (tests/test_gpu_nf_matrix.py, tests/test_gpu_bdraw_persist.py, tests/test_nf_matrix_ref.py).
 
-``dispatch_nf`` (csrc/gibbs_bdraw.hip) stamps every b-draw, sweep, likelihood and hyper-MH kernel
+``dispatch_nf`` (csrc/gibbs_bdraw.h) stamps every b-draw, sweep, likelihood and hyper-MH kernel
 out in eight NF classes -- the fixed NFC = 20 / 40 / 60 and, with NF at run time, NTC = NF/16 + 1 =
 1..5 tile rows -- and the fixed-prior block is read in tiles (NMX <= 16), row-major (17..64) or by
 the wide kernel (> 64).  NF_LIST has every class at its smallest, an interior and its largest NF,

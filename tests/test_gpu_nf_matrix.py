@@ -1,4 +1,4 @@
-"""Every NF class of dispatch_nf (csrc/gibbs_bdraw.hip) on every fixed-block layout and both
+"""Every NF class of dispatch_nf (csrc/gibbs_bdraw.h) on every fixed-block layout and both
 one-chain sweep shapes.
 
 The kernels k_bdraw, k_lnlike_marg and k_sweep_freespec / k_sweep_freespec_rm exist in eight NF

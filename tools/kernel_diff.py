@@ -1,8 +1,12 @@
-"""Compare the kernels of two device-assembly files of one translation unit (refactor guard).
+"""Compare the kernels of two device-assembly files (refactor guard).
 
-    hipcc <the Makefile's flags for the file> --cuda-device-only -S gibbs_bdraw.hip -o old.s   # at the old commit
-    hipcc <the same flags>                    --cuda-device-only -S gibbs_bdraw.hip -o new.s   # at the new one
+    hipcc <the Makefile's flags for the file> --cuda-device-only -S gibbs_sweep.hip -o old.s   # at the old commit
+    hipcc <the same flags>                    --cuda-device-only -S gibbs_sweep.hip -o new.s   # at the new one
     python tools/kernel_diff.py old.s new.s
+
+Kernels are matched by mangled name, so code that moved between translation units compares as well:
+concatenate the .s files of the units on each side (cat gibbs_bdraw.s gibbs_bdraw_tiled.s gibbs_lnlike.s
+gibbs_sweep.s > new.s for the b-draw family, each compiled with its own flags of the Makefile).
 
 Each file is cut into kernels by mangled name: the text from the kernel's label to its .Lfunc_end
 (the code, then the .amdhsa_kernel descriptor block, compared separately).  The function index in

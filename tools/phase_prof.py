@@ -1,7 +1,10 @@
 """Per-phase cycle breakdown of the tile b-draw inside the fused sweep kernel.
 
-Needs the GS_PHASE_PROF variant: make -C pulsar_timing_gibbsspec_amd/csrc variant NAME=phase
-EXTRA="-DGS_TILE_MINW=2 -DGS_PHASE_PROF"; run with GS_LIB_PATH pointing at it.
+Needs the GS_PHASE_PROF variant of the sweep's unit (gibbs_sweep.hip, the variant-one default: the
+phase counters and their accessor gs_debug_phase_cycles are that unit's own):
+make -C pulsar_timing_gibbsspec_amd/csrc variant-one NAME=phase EXTRA="-DGS_TILE_MINW=2 -DGS_PHASE_PROF";
+run with GS_LIB_PATH pointing at it.  (GS_TILE_MINW is read by every unit of the b-draw family; only the
+sweep is profiled here, so the other units keep their default build.  variant-bdraw rebuilds all four.)
 """
 import ctypes
 import os
