@@ -448,6 +448,30 @@ int gs_chain_summary(gs_ctx* ctx, int n_chain, int n_param, const double* x, int
                      int64_t sweep, int64_t burn, int n_bins, const double* lo, const double* hi,
                      const double* scale, const double* mid, double* s1, double* s2, int64_t* counts,
                      int64_t* outside, int64_t* n_acc);
+/*
+ * gs_chain_summary for a block of rows of n_group groups of n_chain chains, with one histogram per
+ * group -- the record blocks of the single-pulsar samplers, where a group is a pulsar:
+ *   v(r, g, c, j) = x[r * row_stride + (g * n_chain + c) * n_param + j],
+ *   row_stride >= n_group * n_chain * n_param.
+ * Per group the semantics are gs_chain_summary's, word for word: row r belongs to sweep `sweep + r`
+ * (+ the attached counter) and is skipped below `burn`; d = v - mid[j]: s1 += d in ascending r onto
+ * the stored value (the sequential sum bit for bit), s2 += d * d (an fma is allowed); the bin is
+ * min((int)floor((v - lo[j]) * scale[j]), n_bins - 1); NaN, +-inf and anything beyond [lo, hi] count
+ * in `outside` and still enter s1 and s2.  lo, hi, scale, mid [n_param] are shared by the groups and
+ * the rows are common to them: n_acc[0] grows once per call.  s1, s2 [n_group * n_chain x n_param];
+ * counts [n_group x n_param x n_bins]; outside [n_group x n_param]; n_acc [1].  Integer atomics
+ * only: every result is reproducible.  One launch: lanes run along the flat (c, j) index of a
+ * group, so every lane works at any n_param, and a group's table of 32-bit words lives in LDS:
+ * n_param rows of (n_bins + 1) | 1 words (the bins, the row's `outside` word, and one unused word
+ * when n_bins is odd); where n_param * ((n_bins + 1) | 1) exceeds 16384 words (64 KB) the call is
+ * one gs_chain_summary launch per group.
+ * 1 <= n_bins <= 256, n_param >= 1, n_group >= 0, n_chain >= 0, n_rows >= 0,
+ * n_rows * n_group * n_chain < 2^31.
+ */
+int gs_chain_summary_block(gs_ctx* ctx, int n_group, int n_chain, int n_param, const double* x, int n_rows,
+                           int64_t row_stride, int64_t sweep, int64_t burn, int n_bins, const double* lo,
+                           const double* hi, const double* scale, const double* mid, double* s1, double* s2,
+                           int64_t* counts, int64_t* outside, int64_t* n_acc);
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate);

@@ -23,7 +23,8 @@ import numpy as np
 
 from . import _lib
 from .engine import DeviceModel
-from .pulsar_gibbs import PulsarBlockGibbs, resolve_seed, sample_free_spectrum
+from .plumbing import flat_bounds
+from .pulsar_gibbs import PulsarBlockGibbs, resolve_seed, sample_free_spectrum, summary_arguments
 
 
 def balanced_blocks(weights, world):
@@ -98,12 +99,26 @@ class PulsarArrayGibbs(object):
             fixed.append(ph[mask])
         return DeviceModel(self.ctx, T, N, R, [s.gwid for s in self.samplers], fixed)
 
-    def sample(self, xs_list, outdir="./", niter=10000, resume=False, save_every=100, record_bchains=None):
+    def sample(self, xs_list, outdir="./", niter=10000, resume=False, save_every=100, record_bchains=None, *,
+               history="memory", bins=None, burn=None, record_chains=None):
         """Every pulsar's PulsarBlockGibbs.sample (pulsar_gibbs.py:620-710) at once.
         xs_list[p]: pulsar p's initial parameter vector.  Pulsar p writes to
-        ``outdir/<pulsar name>/``.  Returns the list of chain-0 chains."""
+        ``outdir/<pulsar name>/``.  Returns the list of chain-0 chains.
+
+        history="summary", bins, burn, record_chains: as PulsarBlockGibbs.sample -- every chain's
+        posterior accumulated on the device, one histogram per pulsar in one launch per block
+        (gs_chain_summary_block); each pulsar's directory gets its own summary.npz and
+        ``samplers[p].summary`` holds it; record_chains chains of each pulsar reach the host."""
         if len(xs_list) != len(self.samplers):
             raise ValueError(f"{len(xs_list)} initial vectors for {len(self.samplers)} pulsars")
+        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume)
+        if summary is not None:
+            lo, hi = flat_bounds(self.samplers[0].params)
+            for s in self.samplers[1:]:
+                ls, hs = flat_bounds(s.params)
+                if not (np.array_equal(ls, lo) and np.array_equal(hs, hi)):
+                    raise NotImplementedError(f"{s.pulsar_name}: history='summary' bins every pulsar over the "
+                                              "same prior ranges")
         outdirs = [os.path.join(outdir, n) for n in self.pulsars]
         for s, o in zip(self.samplers, outdirs):
             print(f"Creating chain directory: {o}")
@@ -112,5 +127,6 @@ class PulsarArrayGibbs(object):
             np.savetxt(f"{o}/pars_bchain.txt", s.b_param_names, fmt="%s")
         model = self._model(xs_list)
         self._runner = sample_free_spectrum(self.samplers, model, xs_list, outdirs, niter, resume, save_every,
-                                            psr_base=self.psr_base, record_bchains=record_bchains)
+                                            psr_base=self.psr_base, record_bchains=record_bchains,
+                                            summary=summary)
         return [s.chain for s in self.samplers]

@@ -810,6 +810,35 @@ int gs_chain_summary(gs_ctx* ctx, int n_chain, int n_param, const double* x, int
   return after_launch("k_chain_summary");
 }
 
+int gs_chain_summary_block(gs_ctx* ctx, int n_group, int n_chain, int n_param, const double* x, int n_rows,
+                           int64_t row_stride, int64_t sweep, int64_t burn, int n_bins, const double* lo,
+                           const double* hi, const double* scale, const double* mid, double* s1, double* s2,
+                           int64_t* counts, int64_t* outside, int64_t* n_acc) {
+  if (!ctx) return fail_arg(1, "ctx is NULL");
+  if (n_group < 0) return fail_arg(2, "n_group must be >= 0");
+  if (n_chain < 0) return fail_arg(3, "n_chain must be >= 0");
+  if (n_param <= 0) return fail_arg(4, "n_param must be >= 1");
+  if (!x) return fail_arg(5, "x is NULL");
+  if (n_rows < 0) return fail_arg(6, "n_rows must be >= 0");
+  if ((__int128)n_rows * n_group * n_chain > 0x7fffffffLL)  // a workgroup's 32-bit table words
+    return fail_arg(6, "n_rows * n_group * n_chain must be below 2^31");
+  if ((__int128)row_stride < (__int128)n_group * n_chain * n_param)
+    return fail_arg(7, "row_stride must be >= n_group * n_chain * n_param");
+  if (n_bins < 1 || n_bins > 256) return fail_arg(10, "n_bins must be in 1..256");
+  if (!lo || !hi || !scale || !mid) return fail_arg(11, "NULL lo / hi / scale / mid");
+  if (!s1 || !s2) return fail_arg(15, "NULL s1 / s2");
+  if (!counts || !outside || !n_acc) return fail_arg(17, "NULL counts / outside / n_acc");
+  SummaryBlockArgs b;
+  SummaryArgs& a = b.s;
+  a.n_chain = n_chain; a.n_param = n_param; a.n_rows = n_rows; a.n_bins = n_bins; a.strip = 0;
+  a.row_stride = row_stride; a.sweep = sweep; a.burn = burn; a.sweep_dev = ctx->sweep_dev;
+  a.x = x; a.lo = lo; a.hi = hi; a.scale = scale; a.mid = mid; a.s1 = s1; a.s2 = s2;
+  a.counts = counts; a.outside = outside; a.n_acc = n_acc;
+  b.n_group = n_group; b.g0 = 0; b.strips = 0; b.strip = 0;
+  launch_chain_summary_block(ctx->stream, b);
+  return after_launch("k_chain_summary_block");
+}
+
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate) {

@@ -271,6 +271,14 @@ struct SummaryArgs {  // gs_chain_summary (gibbs_summary.hip)
   int64_t *counts, *outside, *n_acc;
 };
 int launch_chain_summary(hipStream_t s, SummaryArgs a);
+struct SummaryBlockArgs {  // gs_chain_summary_block (gibbs_summary.hip)
+  SummaryArgs s;  // n_chain: chains per group; x, s1, s2, counts, outside: group 0's
+  int n_group;
+  int g0;          // first group of this launch (set by the launcher)
+  int strips;      // workgroups per group (set by the launcher)
+  int64_t strip;   // (c, j) entries per workgroup (set by the launcher)
+};
+int launch_chain_summary_block(hipStream_t s, SummaryBlockArgs a);
 int launch_phi_powerlaw(hipStream_t s, int n_psr, int n_chain, int n_f, const double* x, int ldx,
                         const int32_t* pl_col, const double* lnphi, double* out);
 

@@ -443,86 +443,144 @@ class ChainSummary:
     counts what falls beyond, NaN and +-inf included), and the number of rows taken, ``n_acc``.
     Sweeps below ``burn`` are skipped on the device.  ``accumulate(eng)`` is one launch on the
     engine's current state -- a graph node inside PTAChains.capture; ``finalize()`` reduces over the
-    chains (mean, variance, Gelman-Rubin R-hat) with ordinary torch work on the context's stream."""
+    chains (mean, variance, Gelman-Rubin R-hat) with ordinary torch work on the context's stream.
 
-    def __init__(self, ctx, n_chain, n_param, lo, hi, n_bins=64, burn=0):
+    n_group > 1: n_group groups of n_chain chains each (the pulsars of a single-pulsar sampler's
+    record block) share lo and hi and keep a histogram and a reduction each: ``counts``, ``outside``
+    and every array of ``finalize()`` gain a leading group axis.  ``accumulate_block`` takes a block
+    of recorded rows (gs_chain_summary_block)."""
+
+    def __init__(self, ctx, n_chain, n_param, lo, hi, n_bins=64, burn=0, n_group=1):
         self.ctx, self.n_chain, self.n_param = ctx, int(n_chain), int(n_param)
-        self.n_bins, self.burn = int(n_bins), int(burn)
+        self.n_bins, self.burn, self.n_group = int(n_bins), int(burn), int(n_group)
         if not 1 <= self.n_bins <= 256:
             raise ValueError(f"n_bins must be in 1..256 (got {n_bins})")
+        if self.n_group < 1:
+            raise ValueError(f"n_group must be >= 1 (got {n_group})")
         lo, hi = np.asarray(lo, float).ravel(), np.asarray(hi, float).ravel()
         if lo.shape != (self.n_param,) or hi.shape != (self.n_param,):
             raise ValueError(f"lo and hi must hold {self.n_param} bounds each")
         if not (hi > lo).all():
             raise ValueError("every histogram range needs hi > lo")
         dev = ctx.device
+        G = (self.n_group,) if self.n_group > 1 else ()
         self.lo_host, self.hi_host = lo, hi
         self.lo, self.hi = _t(lo, torch.float64, dev), _t(hi, torch.float64, dev)
         self.scale = _t(self.n_bins / (hi - lo), torch.float64, dev)       # the kernel's bin = floor((v - lo) scale)
         self.mid = _t((lo + hi) / 2, torch.float64, dev)
-        self.s1 = torch.zeros(self.n_chain, self.n_param, dtype=torch.float64, device=dev)
+        self.s1 = torch.zeros(self.n_group * self.n_chain, self.n_param, dtype=torch.float64, device=dev)
         self.s2 = torch.zeros_like(self.s1)
-        self.counts = torch.zeros(self.n_param, self.n_bins, dtype=torch.int64, device=dev)
-        self.outside = torch.zeros(self.n_param, dtype=torch.int64, device=dev)
+        self.counts = torch.zeros(*G, self.n_param, self.n_bins, dtype=torch.int64, device=dev)
+        self.outside = torch.zeros(*G, self.n_param, dtype=torch.int64, device=dev)
         self.n_acc = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._packed = None                        # event of a pack_behind the next accumulation waits for
+
+    def _after_pack(self):
+        if self._packed is not None:
+            self.ctx.stream.wait_event(self._packed)
+            self._packed = None
 
     def accumulate(self, eng):
         """Add the engine's current state x (the row of sweep eng.it) for every chain."""
-        if (eng.C, eng.n_param) != (self.n_chain, self.n_param):
-            raise ValueError(f"the summary holds {self.n_chain} chains of {self.n_param} parameters, the engine "
-                             f"{eng.C} of {eng.n_param}")
+        self._after_pack()
+        if (eng.C, eng.n_param) != (self.n_chain, self.n_param) or self.n_group != 1:
+            raise ValueError(f"the summary holds {self.n_group} x {self.n_chain} chains of {self.n_param} "
+                             f"parameters, the engine {eng.C} of {eng.n_param}")
         check(self.ctx.lib.gs_chain_summary(
             self.ctx.handle, self.n_chain, self.n_param, ptr(eng.x), 1, self.n_chain * self.n_param, eng.it,
             self.burn, self.n_bins, ptr(self.lo), ptr(self.hi), ptr(self.scale), ptr(self.mid), ptr(self.s1),
             ptr(self.s2), ptr(self.counts), ptr(self.outside), ptr(self.n_acc)), "gs_chain_summary")
 
+    def accumulate_block(self, x_block, first_sweep, n_rows):
+        """Add rows [:n_rows] of x_block (rows, n_group * n_chain, n_param), the states before sweeps
+        first_sweep, first_sweep + 1, ...: one launch on the context's stream.  The rows may be
+        padded (any row stride >= a row); inside a row the block must be contiguous."""
+        if x_block.dim() != 3 or tuple(x_block.shape[1:]) != (self.n_group * self.n_chain, self.n_param):
+            raise ValueError(f"the summary holds {self.n_group} x {self.n_chain} chains of {self.n_param} "
+                             f"parameters, the block is {tuple(x_block.shape)}")
+        if x_block.dtype != torch.float64 or x_block.device != self.s1.device:
+            raise ValueError(f"the block must be float64 on {self.s1.device} (got {x_block.dtype} on "
+                             f"{x_block.device})")
+        row = self.n_group * self.n_chain * self.n_param
+        if not x_block[:1].is_contiguous() or (x_block.shape[0] > 1 and x_block.stride(0) < row):
+            raise ValueError(f"the block's rows must be contiguous and at least {row} apart (strides "
+                             f"{tuple(x_block.stride())})")
+        if not 0 <= int(n_rows) <= x_block.shape[0]:
+            raise ValueError(f"n_rows = {n_rows} of a block of {x_block.shape[0]} rows")
+        self._after_pack()
+        check(self.ctx.lib.gs_chain_summary_block(
+            self.ctx.handle, self.n_group, self.n_chain, self.n_param, ptr(x_block[:1]), int(n_rows),
+            max(int(x_block.stride(0)), row), int(first_sweep), self.burn, self.n_bins, ptr(self.lo),
+            ptr(self.hi), ptr(self.scale), ptr(self.mid), ptr(self.s1), ptr(self.s2), ptr(self.counts),
+            ptr(self.outside), ptr(self.n_acc)), "gs_chain_summary_block")
+
     # the two buffers a HistoryStreamer carries for a summary: int64 words (as float64 bit
     # patterns) [counts | outside | n_acc] and the reduced moments [mean, var, W, Bn, rhat]
     @property
     def extra_shapes(self):
-        return [(self.n_param * (self.n_bins + 1) + 1,), (5, self.n_param)]
+        k = self.n_group * self.n_param
+        return [(k * (self.n_bins + 1) + 1,), (5, k)]
 
-    def finalize(self):
-        """Device tensors reduced over the C chains, n = n_acc rows each: counts, outside, n,
-        mean = mean_c(m_c) with m_c = mid + s1_c / n, W = mean_c(v_c) with v_c = (s2_c - s1_c^2 / n) /
-        (n - 1), Bn = var_c(m_c, ddof=1), var = sum_c s2_c / (C n) - (sum_c s1_c / (C n))^2 (the pooled
-        variance) and rhat = sqrt(((n - 1) / n W + Bn) / W), NaN where n < 2, C < 2 or W = 0.  No
-        host synchronisation."""
+    def finalize(self, stream=None):
+        """Device tensors reduced over the C chains (of each group), n = n_acc rows each: counts,
+        outside, n, mean = mean_c(m_c) with m_c = mid + s1_c / n, W = mean_c(v_c) with v_c = (s2_c -
+        s1_c^2 / n) / (n - 1), Bn = var_c(m_c, ddof=1), var = sum_c s2_c / (C n) - (sum_c s1_c / (C n))^2
+        (the pooled variance) and rhat = sqrt(((n - 1) / n W + Bn) / W), NaN where n < 2, C < 2 or
+        W = 0.  No host synchronisation.  stream: where the work is queued (default: the context's)."""
         C = self.n_chain
         nan = float("nan")
-        with torch.cuda.stream(self.ctx.stream):
+        with torch.cuda.stream(stream or self.ctx.stream):
             n = self.n_acc.to(torch.float64)                               # [1], stays on the device
-            m_c = self.mid + self.s1 / n
-            v_c = (self.s2 - self.s1 * self.s1 / n) / (n - 1)
-            mean, W = m_c.mean(0), v_c.mean(0)
-            Bn = m_c.var(0, unbiased=True) if C > 1 else torch.full_like(mean, nan)
-            var = self.s2.sum(0) / (C * n) - (self.s1.sum(0) / (C * n)) ** 2
+            s1, s2 = self.s1, self.s2
+            if self.n_group > 1:                                           # (group, chain, parameter)
+                s1, s2 = (s.view(self.n_group, C, self.n_param) for s in (s1, s2))
+            c = s1.dim() - 2                                               # the chain axis
+            m_c = self.mid + s1 / n
+            v_c = (s2 - s1 * s1 / n) / (n - 1)
+            mean, W = m_c.mean(c), v_c.mean(c)
+            Bn = m_c.var(c, unbiased=True) if C > 1 else torch.full_like(mean, nan)
+            var = s2.sum(c) / (C * n) - (s1.sum(c) / (C * n)) ** 2
             rhat = torch.sqrt(((n - 1) / n * W + Bn) / W)
             rhat = torch.where((W > 0) & (n >= 2), rhat, torch.full_like(rhat, nan))
             return dict(counts=self.counts, outside=self.outside, n=self.n_acc, mean=mean, var=var, W=W, Bn=Bn,
                         rhat=rhat)
 
-    def pack(self, ints, reals):
+    def pack(self, ints, reals, stream=None):
         """finalize() into two float64 buffers of ``extra_shapes`` (a streamer slot's)."""
-        f = self.finalize()
-        with torch.cuda.stream(self.ctx.stream):
+        f = self.finalize(stream)
+        with torch.cuda.stream(stream or self.ctx.stream):
             w = ints.view(torch.int64)
-            nb = self.n_param * self.n_bins
+            k = self.n_group * self.n_param
+            nb = k * self.n_bins
             w[:nb].copy_(f["counts"].view(-1))
-            w[nb:nb + self.n_param].copy_(f["outside"])
+            w[nb:nb + k].copy_(f["outside"].view(-1))
             w[-1:].copy_(f["n"])
-            for i, k in enumerate(("mean", "var", "W", "Bn", "rhat")):
-                reals[i].copy_(f[k])
+            for i, name in enumerate(("mean", "var", "W", "Bn", "rhat")):
+                reals[i].copy_(f[name].view(-1))
+
+    def pack_behind(self, stream, ints, reals):
+        """``pack`` on another stream (a streamer's side stream), ordered after what the context's
+        stream holds so far: the three dozen small kernels of finalize() then run beside the next
+        block's sweeps instead of in front of them.  The next accumulate / accumulate_block waits
+        for it on the device, so the accumulators it reads do not move under it."""
+        ready = torch.cuda.Event()
+        ready.record(self.ctx.stream)
+        stream.wait_event(ready)
+        self.pack(ints, reals, stream=stream)
+        self._packed = torch.cuda.Event()
+        self._packed.record(stream)
 
     def unpack(self, ints, reals):
         """Host arrays of what ``pack`` wrote (ints, reals: the fetched host tensors)."""
+        G = (self.n_group,) if self.n_group > 1 else ()
         w = ints.numpy().view(np.int64)
-        nb = self.n_param * self.n_bins
-        out = dict(counts=w[:nb].reshape(self.n_param, self.n_bins).copy(),
-                   outside=w[nb:nb + self.n_param].copy(), n=np.int64(w[-1]))
+        k = self.n_group * self.n_param
+        nb = k * self.n_bins
+        out = dict(counts=w[:nb].reshape(*G, self.n_param, self.n_bins).copy(),
+                   outside=w[nb:nb + k].reshape(*G, self.n_param).copy(), n=np.int64(w[-1]))
         r = reals.numpy()
-        for i, k in enumerate(("mean", "var", "W", "Bn", "rhat")):
-            out[k] = r[i].copy()
+        for i, name in enumerate(("mean", "var", "W", "Bn", "rhat")):
+            out[name] = r[i].reshape(*G, self.n_param).copy()
         return out
 
 

@@ -31,7 +31,7 @@ from .engine import DeviceModel, PTAChains
 from .plumbing import (basis_layout, expand_names, flat_bounds, last_match, matching_indices, power_bounds,
                        vector_to_dict)
 from .pta_hyper import HYPER_WARMUP, HyperSpec, hyper_aclength
-from .pulsar_gibbs import HOST_CHAIN, resolve_seed
+from .pulsar_gibbs import HOST_CHAIN, resolve_seed, write_summary
 
 
 class PTABlockGibbs(object):
@@ -451,10 +451,7 @@ class PTABlockGibbs(object):
 
     def _write_summary(self, outdir, summary):
         """summary.npz: written under a temporary name, then moved into place."""
-        tmp = f"{outdir}/summary.npz.tmp"
-        with open(tmp, "wb") as f:
-            np.savez(f, **summary)
-        os.replace(tmp, f"{outdir}/summary.npz")
+        write_summary(outdir, summary)
 
     def _sample_disk(self, xs, outdir, niter, resume, save_every, flush_final, record_chains, thin, slots,
                      summary=None):

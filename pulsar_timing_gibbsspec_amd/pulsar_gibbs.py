@@ -17,7 +17,9 @@ the same chain files.  The arithmetic runs on the GPU through the C-ABI:
 
 Extensions (keyword-only, reference-equivalent defaults): ``nchains``
 (independent chains, chain 0 is written in the reference layout), ``device``,
-``seed`` (Philox key).
+``seed`` (Philox key); ``sample(history="summary")`` keeps every chain's posterior
+(histograms, moments, R-hat) on the device and only a few chains' rows on the host
+(engine.ChainSummary -> gs_chain_summary_block).
 
 * power-law intrinsic red noise: ``update_red_params`` /
   ``get_lnlikelihood_red`` -> gs_red_mh (:271-329, :549-566), rho|b -> gs_rho_gumbel
@@ -39,8 +41,8 @@ import torch
 from . import _lib
 from .diagnostics import white_aclength
 from .ecorr import EcorrFreeSpectrumChains, EcorrModel, EcorrWhiteChains
-from .engine import DeviceModel, FreeSpectrumChains, HistoryStreamer, check_handoff, grid3
-from .plumbing import (basis_layout, expand_names, last_match, matching_indices, power_bounds,
+from .engine import ChainSummary, DeviceModel, FreeSpectrumChains, HistoryStreamer, check_handoff, grid3
+from .plumbing import (basis_layout, expand_names, flat_bounds, last_match, matching_indices, power_bounds,
                        uniform_bounds, vector_to_dict)
 from .rednoise import (DE_BUFFER, RED_STEPS, RedJumps, RedNoiseChains, powerlaw_loglinear,
                        warmup as red_warmup)
@@ -75,8 +77,40 @@ def save_rows(s, outdir, n, chains=False, bchains=False):
         np.save(f"{outdir}/bchains.npy", s.bchains[:, :n])
 
 
+def write_summary(outdir, summary):
+    """summary.npz of a history="summary" run: written under a temporary name, then moved into
+    place, so a reader never sees half a file."""
+    tmp = f"{outdir}/summary.npz.tmp"
+    with open(tmp, "wb") as f:
+        np.savez(f, **summary)
+    os.replace(tmp, f"{outdir}/summary.npz")
+
+
+def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume):
+    """The history / bins / burn / record_chains keywords of the single-pulsar samplers, checked
+    before anything is touched: None for history="memory", (bins, burn, record_chains) for
+    history="summary"."""
+    if history not in ("memory", "summary"):
+        raise ValueError("history must be 'memory' or 'summary'")
+    if history != "summary":
+        if bins is not None or burn is not None or record_chains is not None:
+            raise ValueError("bins, burn and record_chains need history='summary'")
+        return None
+    bins = 64 if bins is None else bins
+    burn = 0 if burn is None else burn
+    K = 1 if record_chains is None else record_chains
+    for name, v, a, b in (("bins", bins, 1, 256), ("burn", burn, 0, int(niter) - 1),
+                          ("record_chains", K, 1, int(nchains))):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not a <= v <= b:
+            raise ValueError(f"{name} must be an integer in {a}..{b} (got {v!r})")
+    if resume:
+        raise NotImplementedError("resume=True is not wired for history='summary' (the accumulators are "
+                                  "not saved)")
+    return int(bins), int(burn), int(K)
+
+
 def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_every, psr_base=0,
-                         record_bchains=None):
+                         record_bchains=None, summary=None):
     """The free-spectrum sample loop (PulsarBlockGibbs.sample, pulsar_gibbs.py:620-710) for
     one or many pulsars at once: pulsar p of ``model`` is ``samplers[p]``'s PTA, its chains
     are systems p*nchains .. p*nchains + nchains - 1 of one FreeSpectrumChains run (the
@@ -92,7 +126,17 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     record_bchains: keep every chain's b history on the host (``bchains``, bchains.npy);
     default only for nchains <= 16 -- 4096 chains x 10^4 sweeps of b are 25 GB, and chain 0's
     b (the reference's bchain) is what the reference layout needs.  Without it only chain 0's
-    b rows cross PCIe (the rest are recorded in HBM only)."""
+    b rows cross PCIe (the rest are recorded in HBM only).
+
+    summary = (bins, burn, record_chains): history="summary".  The x rows of a block are recorded
+    into HBM slots; only chains 0..record_chains-1 of each pulsar go to the host (``chains`` is
+    (record_chains, niter, n_f), or None for one chain -- the (nchains, niter, n_f) array is never
+    allocated), and every chain's posterior is accumulated on the device behind each block
+    (engine.ChainSummary with one group per pulsar, gs_chain_summary_block; row ii is the state
+    before sweep ii, rows below ``burn`` are skipped).  At every save point and at the end the
+    arrays are reduced on the streamer's side stream (ChainSummary.pack_behind), travel in two
+    more buffers of the streamer's slot and are fetched one block behind, like the rows; each pulsar's summary.npz (the keys of PTABlockGibbs's) is rewritten
+    from them and kept as ``summary`` on its sampler.  b is recorded as in the default mode."""
     P = len(samplers)
     nc = samplers[0].nchains
     ctx = model.ctx
@@ -103,10 +147,13 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     if record_bchains is None:
         record_bchains = nc <= 16
     allb = nc > 1 and bool(record_bchains)
+    # chains whose x rows reach the host, and whether they are kept as ``chains`` / chains.npy
+    K = nc if summary is None else summary[2]
+    multi = K > 1
     for s in samplers:
         s.chain = np.zeros((niter, n_f))
         s.bchain = np.zeros((niter, len(s._b)))
-        s.chains = np.zeros((nc, niter, n_f)) if nc > 1 else None
+        s.chains = np.zeros((K, niter, n_f)) if multi else None
         s.bchains = np.zeros((nc, niter, len(s._b))) if allb else None
         s.iter = 0
     start = 0
@@ -161,7 +208,21 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     # straight into the pinned slots; every chain's b (record_bchains) goes through HBM and the
     # copy engine
     bk = nc if (allb or nc == 1) else 1
-    streamer = HistoryStreamer(ctx, [(blk, P * nc, n_f), (blk, P * bk, model.ldb)], direct=[True, not allb])
+    shapes = [(blk, P * nc, n_f), (blk, P * bk, model.ldb)]
+    summ = None
+    if summary is None:
+        streamer = HistoryStreamer(ctx, shapes, direct=[True, not allb])
+    else:
+        # x rows into HBM slots: the summary kernel reads them there, and the copy engine takes
+        # the first K chains of each pulsar; the reduced arrays of a save point ride in two more
+        # buffers of the slot (a leading axis of 1: the streamer slices rows)
+        lo, hi = flat_bounds(samplers[0].params)
+        summ = ChainSummary(ctx, nc, n_f, lo, hi, n_bins=summary[0], burn=summary[1], n_group=P)
+        streamer = HistoryStreamer(ctx, shapes + [(1,) + tuple(e) for e in summ.extra_shapes],
+                                   views=[lambda t: t.view(t.shape[0], P, nc, n_f)[:, :, :K], None, None, None],
+                                   direct=[False, not allb, False, False])
+        for s in samplers:
+            s.summary = None
     bstride = bk
     # failed (non-PD) draws, surfaced per block as they happen: the kernels keep b and count
     # (gs_ctx_set_fail_counts); each block's counts reach pinned memory behind the block
@@ -171,7 +232,8 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     fc_seen = [int(runner.fail_count.sum())]
 
     def consume(slot, ii, nxt):
-        xh, bh = (t.numpy() for t in streamer.fetch(slot))
+        xh, bh, *sum_h = streamer.fetch(slot)
+        xh, bh = xh.numpy().reshape(nxt - ii, P, K, n_f), bh.numpy()
         fc_ev[slot].synchronize()
         # a chain whose hand-off wait expired (info = -1) was not advanced: fail loudly
         check_handoff(info_host[slot])
@@ -186,25 +248,39 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
             fc_seen[0] = tot
         last = nxt - 1
         save = last % save_every == 0 and last > 0
+        if summ is not None and (save or nxt == niter):
+            # rows [burn, last] of every chain, reduced on the device behind the block
+            red = summ.unpack(sum_h[0][0], sum_h[1][0])
+            for p, (s, o) in enumerate(zip(samplers, outdirs)):
+                s.summary = dict(names=np.array(s.param_names), lo=summ.lo_host, hi=summ.hi_host,
+                                 n_bins=np.int64(summ.n_bins), burn=np.int64(summ.burn), nchains=np.int64(nc),
+                                 rows=np.int64(nxt),
+                                 **{k: v if P == 1 or k == "n" else v[p].copy() for k, v in red.items()})
+                s._write_summary(o, s.summary)
         for p, (s, o) in enumerate(zip(samplers, outdirs)):
-            xp = xh[:, p * nc:(p + 1) * nc]
+            xp = xh[:, p]
             bp = bh[:, p * bstride:(p + 1) * bstride, :m[p]]
             s.chain[ii:nxt] = xp[:, 0]
             s.bchain[ii:nxt] = bp[:, 0]
-            if nc > 1:
+            if multi:
                 s.chains[:, ii:nxt] = np.moveaxis(xp, 1, 0)
             if allb:
                 s.bchains[:, ii:nxt] = np.moveaxis(bp, 1, 0)
             s.iter = last
             if save:
-                save_rows(s, o, last + 1, nc > 1, allb)
+                save_rows(s, o, last + 1, multi, allb)
 
     ii, slot, pending = start, 0, None
     while ii < niter:
         nxt = min(niter, (ii // save_every + 1) * save_every + 1)
         n = nxt - ii
-        xr, br = streamer.buffers(slot, n)
+        xr, br, *sum_d = streamer.buffers(slot, n)
         runner.run(n, x_rec=xr, b_rec=br, record_b_chains=bk)
+        if summ is not None:
+            summ.accumulate_block(xr, ii, n)
+            if ((nxt - 1) % save_every == 0 and nxt > 1) or nxt == niter:
+                # reduced on the side stream, in front of the slot's copies and beside the next block
+                summ.pack_behind(streamer.side, sum_d[0][0], sum_d[1][0])
         with torch.cuda.stream(ctx.stream):
             fc_host[slot].copy_(runner.fail_count, non_blocking=True)
             info_host[slot].copy_(runner.info, non_blocking=True)
@@ -735,14 +811,34 @@ class PulsarBlockGibbs(object):
             raise NotImplementedError("gw rho parameters must be the whole parameter vector")
 
     def sample(self, xs, outdir="./", niter=10000, resume=False, save_every=100, *, flush_final=False,
-               record_bchains=None):
+               record_bchains=None, history="memory", bins=None, burn=None, record_chains=None):
         """PulsarBlockGibbs.sample (pulsar_gibbs.py:620-710) as persistent device sweeps.
 
         Chain row ii holds the state BEFORE sweep ii (row 0 = xs, bchain[0] = 0).
         Files: pars_chain.txt, pars_bchain.txt, chain.npy, bchain.npy (chain 0,
         rows [:ii+1] written at ii % 100 == 0, ii > 0, as the reference), and with
-        nchains > 1 also chains.npy / bchains.npy (leading chain axis)."""
+        nchains > 1 also chains.npy / bchains.npy (leading chain axis).
+
+        history="summary" (free-spectrum-only models): every chain's posterior is accumulated on
+        the device and only ``record_chains`` chains (default 1: chain 0, as the reference keeps)
+        cross to the host.  chain.npy and bchain.npy are the default mode's byte for byte;
+        ``chains`` / chains.npy hold the recorded chains, (record_chains, niter, n_f), when there is
+        more than one (else ``chains`` is None and no chains.npy is written): host memory does not
+        grow with nchains x niter.  summary.npz, rewritten at every save point and at the end, has
+        the keys of PTABlockGibbs.sample(history="summary")'s file: per parameter a histogram of
+        ``bins`` bins (1..256) over its prior range pooled over the chains, mean, pooled variance
+        and the Gelman-Rubin W, Bn and R-hat, over every row ii >= ``burn`` (0..niter-1);
+        ``self.summary`` holds the last one written.  ``bins`` defaults to 64, ``burn`` to 0 and
+        ``record_chains`` to 1; given with any other history they raise ValueError.  Files the mode
+        does not write are left alone: a chains.npy that an earlier run left in ``outdir`` stays
+        beside the new summary.npz when record_chains is 1.  resume=True is not wired for this
+        mode."""
+        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume)
         self._check_device_loop(xs)
+        if summary is not None and (self._red_loop() or self._ecorr_loop() or self._white_loop()):
+            raise NotImplementedError(
+                "history='summary' is wired for free-spectrum-only models (the fused sweep); the red-noise, "
+                "ECORR and white-noise sample loops record blocks of the same layout and can follow")
         print(f"Creating chain directory: {outdir}")
         os.makedirs(outdir, exist_ok=True)
         np.savetxt(f"{outdir}/pars_chain.txt", self.param_names, fmt="%s")
@@ -764,10 +860,14 @@ class PulsarBlockGibbs(object):
                 self._flush(outdir)
             return out
         sample_free_spectrum([self], self._model(xs), [xs], [outdir], niter, resume, save_every,
-                             record_bchains=record_bchains)
+                             record_bchains=record_bchains, summary=summary)
         if flush_final:
             self._flush(outdir)
         return self.chain
+
+    def _write_summary(self, outdir, summary):
+        """summary.npz: written under a temporary name, then moved into place."""
+        write_summary(outdir, summary)
 
     def _flush(self, outdir):
         """flush_final=True: also write the rows after the last multiple of
