@@ -472,6 +472,50 @@ int gs_chain_summary_block(gs_ctx* ctx, int n_group, int n_chain, int n_param, c
                            int64_t row_stride, int64_t sweep, int64_t burn, int n_bins, const double* lo,
                            const double* hi, const double* scale, const double* mid, double* s1, double* s2,
                            int64_t* counts, int64_t* outside, int64_t* n_acc);
+/*
+ * Pooled autocovariance of the chains of a block layout, up to lag max_lag = L -- what
+ * sample(history="summary", acf_lags=L) of the single-pulsar samplers reports.  For one group (a
+ * pulsar) of C = n_chain chains with n post-burn rows v_c,t in sweep order and m_c chain c's own
+ * mean,
+ *   acov[j][k] = 1 / (C n) sum_c sum_{t=0}^{n-1-k} (v_c,t - m_c)(v_c,t+k - m_c),  k = 0 .. L,
+ * and 0 for k >= n: biased (/ n), each chain's mean removed, averaged over the chains -- the
+ * estimator of diagnostics.pooled_iat, restated on the host as diagnostics.acov_chains.
+ *
+ * gs_chain_acf_state_size: the doubles of one opaque state buffer for these shapes (-1 for shapes
+ * the entries reject).  All zeros means empty.  The layout belongs to the library: per chain and
+ * parameter the sum of d = v - mid[j], the first L and the last L post-burn values, and the
+ * lagged product sums pooled per workgroup; 8 + T (1 + 2 L) + (partials) doubles,
+ * T = n_group * n_chain * n_param.
+ *
+ * gs_chain_acf_block adds one block of rows; layout, row_stride, burn and the sweep counter are
+ * gs_chain_summary_block's, word for word: v(r, g, c, j) = x[r * row_stride + (g * n_chain + c) *
+ * n_param + j], row r belongs to sweep `sweep + r` (+ the attached counter) and is skipped below
+ * `burn`.  Pairs whose earlier member came in an earlier call, up to L rows back, are counted from
+ * the values the state keeps (blocks may be shorter than L); nothing outside `state` is relied on
+ * between calls.  mid [n_param] must be the same in every call on one state.  Three launches: the
+ * product sums (a workgroup owns a fixed strip of one group's chains and 32 (chain, parameter)
+ * lanes, stages their window of rows in 60 KB of LDS, its threads split the lags and keep their
+ * sums in registers with t ascending; the workgroup's chains are summed in a fixed order into its
+ * own partial), the per-chain values, and the row count.
+ *
+ * gs_chain_acf_reduce removes the chains' means and averages over them:
+ *   sum_t (d_t - m)(d_t+k - m) = P_k - m (2 s1 - F_k - E_k) + (n - k) m^2,  m = s1 / n,
+ * P_k the lagged product sum, F_k / E_k the sums of the chain's first / last k values.  It writes
+ * acov [n_group x n_param x (L + 1)] and n [1] (the post-burn rows taken) and does not modify
+ * `state`: save points may call it repeatedly.
+ *
+ * No floating-point atomics: the order of every sum depends on the shapes and the call sequence
+ * only, so every result is reproducible run to run.  A non-finite value makes acov NaN for its
+ * (group, parameter), every lag, and leaves every other parameter and group correct.
+ * 1 <= max_lag <= 4096, n_param >= 1, n_group >= 0, n_chain >= 0, n_rows >= 0, row_stride >=
+ * n_group * n_chain * n_param, n_group * max(n_param, max_lag) < 2^30.
+ */
+int64_t gs_chain_acf_state_size(int n_group, int n_chain, int n_param, int max_lag);
+int gs_chain_acf_block(gs_ctx* ctx, int n_group, int n_chain, int n_param, const double* x, int n_rows,
+                       int64_t row_stride, int64_t sweep, int64_t burn, int max_lag, const double* mid,
+                       double* state);
+int gs_chain_acf_reduce(gs_ctx* ctx, int n_group, int n_chain, int n_param, int max_lag, const double* state,
+                        double* acov, int64_t* n);
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate);

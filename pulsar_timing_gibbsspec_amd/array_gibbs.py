@@ -100,7 +100,7 @@ class PulsarArrayGibbs(object):
         return DeviceModel(self.ctx, T, N, R, [s.gwid for s in self.samplers], fixed)
 
     def sample(self, xs_list, outdir="./", niter=10000, resume=False, save_every=100, record_bchains=None, *,
-               history="memory", bins=None, burn=None, record_chains=None):
+               history="memory", bins=None, burn=None, record_chains=None, acf_lags=None):
         """Every pulsar's PulsarBlockGibbs.sample (pulsar_gibbs.py:620-710) at once.
         xs_list[p]: pulsar p's initial parameter vector.  Pulsar p writes to
         ``outdir/<pulsar name>/``.  Returns the list of chain-0 chains.
@@ -108,10 +108,13 @@ class PulsarArrayGibbs(object):
         history="summary", bins, burn, record_chains: as PulsarBlockGibbs.sample -- every chain's
         posterior accumulated on the device, one histogram per pulsar in one launch per block
         (gs_chain_summary_block); each pulsar's directory gets its own summary.npz and
-        ``samplers[p].summary`` holds it; record_chains chains of each pulsar reach the host."""
+        ``samplers[p].summary`` holds it; record_chains chains of each pulsar reach the host.
+        acf_lags=L: as PulsarBlockGibbs.sample -- each pulsar's summary also holds its own pooled
+        autocovariance up to lag L with the IAT and ESS of every parameter (gs_chain_acf_block, one
+        group per pulsar; resume and the spread over groups of chains are not covered)."""
         if len(xs_list) != len(self.samplers):
             raise ValueError(f"{len(xs_list)} initial vectors for {len(self.samplers)} pulsars")
-        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume)
+        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume, acf_lags)
         if summary is not None:
             lo, hi = flat_bounds(self.samplers[0].params)
             for s in self.samplers[1:]:

@@ -839,6 +839,60 @@ int gs_chain_summary_block(gs_ctx* ctx, int n_group, int n_chain, int n_param, c
   return after_launch("k_chain_summary_block");
 }
 
+// the shape arguments the three gs_chain_acf_* entries share; 0 or the failing argument's index
+static int acf_shape(int n_group, int n_chain, int n_param, int max_lag, int i_lag) {
+  if (n_group < 0) return fail_arg(2, "n_group must be >= 0");
+  if (n_chain < 0) return fail_arg(3, "n_chain must be >= 0");
+  if (n_param <= 0) return fail_arg(4, "n_param must be >= 1");
+  if (max_lag < 1 || max_lag > 4096) return fail_arg(i_lag, "max_lag must be in 1..4096");
+  // launch grids: workgroups of the block kernel (at most 512 + one per group and parameter
+  // tile) and n_group * max_lag, n_group * n_param blocks of the reduction
+  if ((__int128)n_group * (n_param > max_lag ? n_param : max_lag) > 0x3fffffffLL)
+    return fail_arg(2, "n_group * max(n_param, max_lag) must be below 2^30");
+  return 0;
+}
+
+int64_t gs_chain_acf_state_size(int n_group, int n_chain, int n_param, int max_lag) {
+  if (n_group < 0 || n_chain < 0 || n_param <= 0 || max_lag < 1 || max_lag > 4096) return -1;
+  return acf_plan(n_group, n_chain, n_param, max_lag).size;
+}
+
+int gs_chain_acf_block(gs_ctx* ctx, int n_group, int n_chain, int n_param, const double* x, int n_rows,
+                       int64_t row_stride, int64_t sweep, int64_t burn, int max_lag, const double* mid,
+                       double* state) {
+  if (!ctx) return fail_arg(1, "ctx is NULL");
+  if (int rc = acf_shape(n_group, n_chain, n_param, max_lag, 10)) return rc;
+  if (!x) return fail_arg(5, "x is NULL");
+  if (n_rows < 0) return fail_arg(6, "n_rows must be >= 0");
+  if ((__int128)row_stride < (__int128)n_group * n_chain * n_param)
+    return fail_arg(7, "row_stride must be >= n_group * n_chain * n_param");
+  if (!mid) return fail_arg(11, "mid is NULL");
+  if (!state) return fail_arg(12, "state is NULL");
+  AcfArgs a;
+  a.n_group = n_group; a.n_chain = n_chain; a.n_param = n_param; a.n_rows = n_rows; a.max_lag = max_lag;
+  a.row_stride = row_stride; a.sweep = sweep; a.burn = burn; a.sweep_dev = ctx->sweep_dev;
+  a.x = x; a.mid = mid; a.state = state;
+  a.plan = acf_plan(n_group, n_chain, n_param, max_lag);
+  launch_chain_acf_block(ctx->stream, a);
+  return after_launch("k_chain_acf_block");
+}
+
+int gs_chain_acf_reduce(gs_ctx* ctx, int n_group, int n_chain, int n_param, int max_lag, const double* state,
+                        double* acov, int64_t* n) {
+  if (!ctx) return fail_arg(1, "ctx is NULL");
+  if (int rc = acf_shape(n_group, n_chain, n_param, max_lag, 5)) return rc;
+  if (!state) return fail_arg(6, "state is NULL");
+  if (!acov) return fail_arg(7, "acov is NULL");
+  if (!n) return fail_arg(8, "n is NULL");
+  AcfArgs a;
+  a.n_group = n_group; a.n_chain = n_chain; a.n_param = n_param; a.n_rows = 0; a.max_lag = max_lag;
+  a.row_stride = 0; a.sweep = 0; a.burn = 0; a.sweep_dev = nullptr;
+  a.x = nullptr; a.mid = nullptr; a.state = const_cast<double*>(state);
+  a.plan = acf_plan(n_group, n_chain, n_param, max_lag);
+  launch_chain_acf_reduce(ctx->stream, a, acov, n);
+  return after_launch("k_chain_acf_finish");
+}
+
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate) {

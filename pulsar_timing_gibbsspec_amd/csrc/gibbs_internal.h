@@ -279,6 +279,25 @@ struct SummaryBlockArgs {  // gs_chain_summary_block (gibbs_summary.hip)
   int64_t strip;   // (c, j) entries per workgroup (set by the launcher)
 };
 int launch_chain_summary_block(hipStream_t s, SummaryBlockArgs a);
+struct AcfPlan {  // gs_chain_acf_* (gibbs_acf.hip): fixed by (n_group, n_chain, n_param, max_lag) alone
+  int jt;            // parameter lanes of a workgroup: the power of two >= min(n_param, 32)
+  int ct;            // chain lanes: 32 / jt chains per pass
+  int njt;           // parameter tiles
+  int64_t cs, ns;    // chains per workgroup, workgroups per (group, parameter tile)
+  int64_t T;         // flat entries n_group * n_chain * n_param
+  int64_t off_s1, off_head, off_tail, off_part, size;  // the state's arrays and its length, in doubles
+};
+AcfPlan acf_plan(int n_group, int n_chain, int n_param, int max_lag);
+struct AcfArgs {
+  int n_group, n_chain, n_param, n_rows, max_lag;
+  int64_t row_stride, sweep, burn;
+  const int64_t* sweep_dev;  // ctx sweep counter (graph replay) or NULL
+  const double *x, *mid;
+  double* state;
+  AcfPlan plan;
+};
+int launch_chain_acf_block(hipStream_t s, AcfArgs a);
+int launch_chain_acf_reduce(hipStream_t s, AcfArgs a, double* acov, int64_t* n);
 int launch_phi_powerlaw(hipStream_t s, int n_psr, int n_chain, int n_f, const double* x, int ldx,
                         const int32_t* pl_col, const double* lnphi, double* out);
 

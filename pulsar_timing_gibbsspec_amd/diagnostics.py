@@ -151,6 +151,64 @@ def summarize_chains(X, lo, hi, n_bins):
                 rhat=f(rhat))
 
 
+def acov_chains(X, max_lag):
+    """Host restatement of the on-device pooled autocovariance (gs_chain_acf_block /
+    gs_chain_acf_reduce, sample(history="summary", acf_lags=L)) for X (chains, n, k), in numpy long
+    double: pooled_iat's estimator truncated at max_lag,
+      acov[j, lag] = 1 / (C n) sum_c sum_{t=0}^{n-1-lag} (X_ctj - m_cj) (X_c,t+lag,j - m_cj),
+    m_cj chain c's own mean of column j (biased, / n, averaged over the chains), and 0 for
+    lag >= n.  Returns (k, max_lag + 1) doubles."""
+    X = np.asarray(X, float)
+    C, n, k = X.shape
+    Lg = int(max_lag)
+    d = X.astype(np.longdouble)
+    if n:
+        d = d - d.mean(axis=1, keepdims=True)
+    out = np.zeros((k, Lg + 1), np.longdouble)
+    for lag in range(min(Lg + 1, n)):
+        out[:, lag] = (d[:, :n - lag] * d[:, lag:]).sum(axis=(0, 1)) / np.longdouble(C * n)
+    return np.asarray(out, float)
+
+
+def iat_from_acov(acov, c=5.0):
+    """(iat, window) per parameter from acov (..., L + 1), a pooled autocovariance up to lag L
+    (acov_chains, a summary.npz's ``acov``): tau(M) = 2 sum_{k <= M} acov[k] / acov[0] - 1 at the
+    smallest M <= L with M >= c tau(M) (Sokal's window, as pooled_iat), clamped below at 1.  Where no
+    such M exists within L the window is -1 and iat = max(tau(L), 1): a lower bound, the sum was cut
+    short.  NaN (window -1) where acov[0] is not positive and finite."""
+    a = np.asarray(acov, float)
+    flat = a.reshape(-1, a.shape[-1])
+    tau_out = np.full(flat.shape[0], np.nan)
+    win = np.full(flat.shape[0], -1, np.int64)
+    lags = np.arange(flat.shape[1])
+    for i, row in enumerate(flat):
+        if not (np.isfinite(row[0]) and row[0] > 0):
+            continue
+        tau = 2.0 * np.cumsum(row / row[0]) - 1.0
+        ok = lags >= c * tau                   # False for a NaN tau
+        if ok.any():
+            win[i] = int(np.argmax(ok))
+            tau_out[i] = max(tau[win[i]], 1.0)
+        else:
+            tau_out[i] = max(tau[-1], 1.0) if np.isfinite(tau[-1]) else np.nan
+    return tau_out.reshape(a.shape[:-1]), win.reshape(a.shape[:-1])
+
+
+def acf_summary(acov, n, nchains, c=5.0):
+    """The keys a summary.npz gains with acf_lags, from acov (k, L + 1) over n rows of nchains
+    chains: iat and iat_window (iat_from_acov), ess_per_sweep = 1 / iat, ess = nchains n / iat and
+    ess_se = ess_per_sweep sqrt(2 (2 M + 1) / (nchains n)) -- Sokal's asymptotic term, (a) of
+    ess_table; NaN where the window was not reached within L.  The spread over groups of chains,
+    ess_table's term (b), needs the chains themselves and is not estimated."""
+    tau, M = iat_from_acov(acov, c)
+    N = float(nchains) * float(n)
+    with np.errstate(all="ignore"):
+        per = 1.0 / tau
+        se = np.where(M >= 0, per * np.sqrt(2.0 * (2.0 * M + 1.0) / N), np.nan) if N > 0 else np.full_like(per, np.nan)
+    return dict(acf_lags=np.int64(np.shape(acov)[-1] - 1), acov=np.asarray(acov, float), iat=tau, iat_window=M,
+                ess_per_sweep=per, ess=N * per, ess_se=se)
+
+
 def hist_quantiles(counts, lo, hi, q):
     """Quantile(s) q of histograms counts (k, n_bins) over [lo, hi] (k,), e.g. a summary.npz's: linear
     interpolation inside the bin where the cumulative count crosses q x total (the first non-empty

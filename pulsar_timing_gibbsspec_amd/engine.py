@@ -448,15 +448,25 @@ class ChainSummary:
     n_group > 1: n_group groups of n_chain chains each (the pulsars of a single-pulsar sampler's
     record block) share lo and hi and keep a histogram and a reduction each: ``counts``, ``outside``
     and every array of ``finalize()`` gain a leading group axis.  ``accumulate_block`` takes a block
-    of recorded rows (gs_chain_summary_block)."""
+    of recorded rows (gs_chain_summary_block).
 
-    def __init__(self, ctx, n_chain, n_param, lo, hi, n_bins=64, burn=0, n_group=1):
+    acf_lags = L > 0: the summary also owns the state of gs_chain_acf_block (L in 1..4096):
+    ``accumulate_block`` queues that entry behind the summary kernel, ``finalize()`` also returns
+    ``acov`` (n_group, n_param, L + 1) -- each group's autocovariance pooled over its chains
+    (diagnostics.acov_chains) -- and pack / pack_behind / unpack carry it in a third buffer of
+    ``extra_shapes``.  ``accumulate`` (one row per call from the live state, the PTA sampler's entry)
+    has no such block of rows and raises NotImplementedError."""
+
+    def __init__(self, ctx, n_chain, n_param, lo, hi, n_bins=64, burn=0, n_group=1, acf_lags=0):
         self.ctx, self.n_chain, self.n_param = ctx, int(n_chain), int(n_param)
         self.n_bins, self.burn, self.n_group = int(n_bins), int(burn), int(n_group)
         if not 1 <= self.n_bins <= 256:
             raise ValueError(f"n_bins must be in 1..256 (got {n_bins})")
         if self.n_group < 1:
             raise ValueError(f"n_group must be >= 1 (got {n_group})")
+        self.acf_lags = int(acf_lags)
+        if not 0 <= self.acf_lags <= 4096:
+            raise ValueError(f"acf_lags must be in 0..4096 (got {acf_lags})")
         lo, hi = np.asarray(lo, float).ravel(), np.asarray(hi, float).ravel()
         if lo.shape != (self.n_param,) or hi.shape != (self.n_param,):
             raise ValueError(f"lo and hi must hold {self.n_param} bounds each")
@@ -474,6 +484,16 @@ class ChainSummary:
         self.outside = torch.zeros(*G, self.n_param, dtype=torch.int64, device=dev)
         self.n_acc = torch.zeros(1, dtype=torch.int64, device=dev)
         self._packed = None                        # event of a pack_behind the next accumulation waits for
+        self.acf_state = self.acov = self.acf_n = None
+        if self.acf_lags:
+            size = int(ctx.lib.gs_chain_acf_state_size(self.n_group, self.n_chain, self.n_param, self.acf_lags))
+            if size < 0:
+                raise ValueError(f"gs_chain_acf_state_size rejected {self.n_group} x {self.n_chain} x "
+                                 f"{self.n_param} at {self.acf_lags} lags")
+            self.acf_state = torch.zeros(size, dtype=torch.float64, device=dev)    # all zeros: empty
+            self.acov = torch.zeros(self.n_group * self.n_param * (self.acf_lags + 1), dtype=torch.float64,
+                                    device=dev)
+            self.acf_n = torch.zeros(1, dtype=torch.int64, device=dev)
 
     def _after_pack(self):
         if self._packed is not None:
@@ -482,6 +502,9 @@ class ChainSummary:
 
     def accumulate(self, eng):
         """Add the engine's current state x (the row of sweep eng.it) for every chain."""
+        if self.acf_lags:
+            raise NotImplementedError("acf_lags needs blocks of recorded rows (accumulate_block); the per-sweep "
+                                      "entry sees one row of the live state")
         self._after_pack()
         if (eng.C, eng.n_param) != (self.n_chain, self.n_param) or self.n_group != 1:
             raise ValueError(f"the summary holds {self.n_group} x {self.n_chain} chains of {self.n_param} "
@@ -513,22 +536,54 @@ class ChainSummary:
             max(int(x_block.stride(0)), row), int(first_sweep), self.burn, self.n_bins, ptr(self.lo),
             ptr(self.hi), ptr(self.scale), ptr(self.mid), ptr(self.s1), ptr(self.s2), ptr(self.counts),
             ptr(self.outside), ptr(self.n_acc)), "gs_chain_summary_block")
+        if self.acf_lags:
+            check(self.ctx.lib.gs_chain_acf_block(
+                self.ctx.handle, self.n_group, self.n_chain, self.n_param, ptr(x_block[:1]), int(n_rows),
+                max(int(x_block.stride(0)), row), int(first_sweep), self.burn, self.acf_lags, ptr(self.mid),
+                ptr(self.acf_state)), "gs_chain_acf_block")
 
     # the two buffers a HistoryStreamer carries for a summary: int64 words (as float64 bit
-    # patterns) [counts | outside | n_acc] and the reduced moments [mean, var, W, Bn, rhat]
+    # patterns) [counts | outside | n_acc] and the reduced moments [mean, var, W, Bn, rhat]; with
+    # acf_lags a third, acov [n_group x n_param x (acf_lags + 1)]
     @property
     def extra_shapes(self):
         k = self.n_group * self.n_param
-        return [(k * (self.n_bins + 1) + 1,), (5, k)]
+        shapes = [(k * (self.n_bins + 1) + 1,), (5, k)]
+        if self.acf_lags:
+            shapes.append((k * (self.acf_lags + 1),))
+        return shapes
 
-    def finalize(self, stream=None):
+    def _acf_reduce(self, out, stream=None):
+        """gs_chain_acf_reduce into ``out`` (a flat device buffer of extra_shapes[2]), queued on
+        ``stream`` (default: the context's).  The state is read only."""
+        main = self.ctx.stream
+        other = stream is not None and stream is not main
+        if other:
+            self.ctx.set_stream(stream)
+        try:
+            check(self.ctx.lib.gs_chain_acf_reduce(
+                self.ctx.handle, self.n_group, self.n_chain, self.n_param, self.acf_lags, ptr(self.acf_state),
+                ptr(out), ptr(self.acf_n)), "gs_chain_acf_reduce")
+        finally:
+            if other:
+                self.ctx.set_stream(main)
+
+    def finalize(self, stream=None, acov_out=None):
         """Device tensors reduced over the C chains (of each group), n = n_acc rows each: counts,
         outside, n, mean = mean_c(m_c) with m_c = mid + s1_c / n, W = mean_c(v_c) with v_c = (s2_c -
         s1_c^2 / n) / (n - 1), Bn = var_c(m_c, ddof=1), var = sum_c s2_c / (C n) - (sum_c s1_c / (C n))^2
         (the pooled variance) and rhat = sqrt(((n - 1) / n W + Bn) / W), NaN where n < 2, C < 2 or
-        W = 0.  No host synchronisation.  stream: where the work is queued (default: the context's)."""
+        W = 0.  No host synchronisation.  stream: where the work is queued (default: the context's).
+        With acf_lags also acov (n_group, n_param, acf_lags + 1) from gs_chain_acf_reduce, written to
+        ``acov_out`` when given (a flat buffer of extra_shapes[2])."""
         C = self.n_chain
         nan = float("nan")
+        acov = {}
+        if self.acf_lags:
+            out = self.acov if acov_out is None else acov_out
+            self._acf_reduce(out, stream)
+            G = (self.n_group,) if self.n_group > 1 else ()
+            acov = dict(acov=out.view(*G, self.n_param, self.acf_lags + 1))
         with torch.cuda.stream(stream or self.ctx.stream):
             n = self.n_acc.to(torch.float64)                               # [1], stays on the device
             s1, s2 = self.s1, self.s2
@@ -543,11 +598,13 @@ class ChainSummary:
             rhat = torch.sqrt(((n - 1) / n * W + Bn) / W)
             rhat = torch.where((W > 0) & (n >= 2), rhat, torch.full_like(rhat, nan))
             return dict(counts=self.counts, outside=self.outside, n=self.n_acc, mean=mean, var=var, W=W, Bn=Bn,
-                        rhat=rhat)
+                        rhat=rhat, **acov)
 
-    def pack(self, ints, reals, stream=None):
-        """finalize() into two float64 buffers of ``extra_shapes`` (a streamer slot's)."""
-        f = self.finalize(stream)
+    def pack(self, ints, reals, acov=None, stream=None):
+        """finalize() into the float64 buffers of ``extra_shapes`` (a streamer slot's)."""
+        if bool(self.acf_lags) != (acov is not None):
+            raise ValueError("the acov buffer goes with acf_lags > 0")
+        f = self.finalize(stream, acov_out=acov)
         with torch.cuda.stream(stream or self.ctx.stream):
             w = ints.view(torch.int64)
             k = self.n_group * self.n_param
@@ -558,7 +615,7 @@ class ChainSummary:
             for i, name in enumerate(("mean", "var", "W", "Bn", "rhat")):
                 reals[i].copy_(f[name].view(-1))
 
-    def pack_behind(self, stream, ints, reals):
+    def pack_behind(self, stream, ints, reals, acov=None):
         """``pack`` on another stream (a streamer's side stream), ordered after what the context's
         stream holds so far: the three dozen small kernels of finalize() then run beside the next
         block's sweeps instead of in front of them.  The next accumulate / accumulate_block waits
@@ -566,12 +623,12 @@ class ChainSummary:
         ready = torch.cuda.Event()
         ready.record(self.ctx.stream)
         stream.wait_event(ready)
-        self.pack(ints, reals, stream=stream)
+        self.pack(ints, reals, acov, stream=stream)
         self._packed = torch.cuda.Event()
         self._packed.record(stream)
 
-    def unpack(self, ints, reals):
-        """Host arrays of what ``pack`` wrote (ints, reals: the fetched host tensors)."""
+    def unpack(self, ints, reals, acov=None):
+        """Host arrays of what ``pack`` wrote (ints, reals, acov: the fetched host tensors)."""
         G = (self.n_group,) if self.n_group > 1 else ()
         w = ints.numpy().view(np.int64)
         k = self.n_group * self.n_param
@@ -581,6 +638,8 @@ class ChainSummary:
         r = reals.numpy()
         for i, name in enumerate(("mean", "var", "W", "Bn", "rhat")):
             out[name] = r[i].reshape(*G, self.n_param).copy()
+        if acov is not None:
+            out["acov"] = acov.numpy().reshape(*G, self.n_param, self.acf_lags + 1).copy()
         return out
 
 

@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .diagnostics import white_aclength
+from .diagnostics import acf_summary, white_aclength
 from .ecorr import EcorrFreeSpectrumChains, EcorrModel, EcorrWhiteChains
 from .engine import ChainSummary, DeviceModel, FreeSpectrumChains, HistoryStreamer, check_handoff, grid3
 from .plumbing import (basis_layout, expand_names, flat_bounds, last_match, matching_indices, power_bounds,
@@ -86,15 +86,15 @@ def write_summary(outdir, summary):
     os.replace(tmp, f"{outdir}/summary.npz")
 
 
-def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume):
-    """The history / bins / burn / record_chains keywords of the single-pulsar samplers, checked
-    before anything is touched: None for history="memory", (bins, burn, record_chains) for
-    history="summary"."""
+def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume, acf_lags=None):
+    """The history / bins / burn / record_chains / acf_lags keywords of the single-pulsar samplers,
+    checked before anything is touched: None for history="memory", (bins, burn, record_chains,
+    acf_lags) for history="summary" (acf_lags 0 when it was not given)."""
     if history not in ("memory", "summary"):
         raise ValueError("history must be 'memory' or 'summary'")
     if history != "summary":
-        if bins is not None or burn is not None or record_chains is not None:
-            raise ValueError("bins, burn and record_chains need history='summary'")
+        if bins is not None or burn is not None or record_chains is not None or acf_lags is not None:
+            raise ValueError("bins, burn, record_chains and acf_lags need history='summary'")
         return None
     bins = 64 if bins is None else bins
     burn = 0 if burn is None else burn
@@ -103,10 +103,16 @@ def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume
                           ("record_chains", K, 1, int(nchains))):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not a <= v <= b:
             raise ValueError(f"{name} must be an integer in {a}..{b} (got {v!r})")
+    if acf_lags is not None:
+        # at least two post-burn rows, and no lag beyond the last pair of them
+        top = min(4096, int(niter) - int(burn) - 1)
+        if isinstance(acf_lags, bool) or not isinstance(acf_lags, (int, np.integer)) or not 1 <= acf_lags <= top:
+            raise ValueError(f"acf_lags must be an integer in 1..{top} (min(4096, niter - burn - 1); got "
+                             f"{acf_lags!r})")
     if resume:
         raise NotImplementedError("resume=True is not wired for history='summary' (the accumulators are "
                                   "not saved)")
-    return int(bins), int(burn), int(K)
+    return int(bins), int(burn), int(K), int(acf_lags or 0)
 
 
 def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_every, psr_base=0,
@@ -128,7 +134,7 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     b (the reference's bchain) is what the reference layout needs.  Without it only chain 0's
     b rows cross PCIe (the rest are recorded in HBM only).
 
-    summary = (bins, burn, record_chains): history="summary".  The x rows of a block are recorded
+    summary = (bins, burn, record_chains, acf_lags): history="summary".  The x rows of a block are recorded
     into HBM slots; only chains 0..record_chains-1 of each pulsar go to the host (``chains`` is
     (record_chains, niter, n_f), or None for one chain -- the (nchains, niter, n_f) array is never
     allocated), and every chain's posterior is accumulated on the device behind each block
@@ -136,7 +142,11 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     before sweep ii, rows below ``burn`` are skipped).  At every save point and at the end the
     arrays are reduced on the streamer's side stream (ChainSummary.pack_behind), travel in two
     more buffers of the streamer's slot and are fetched one block behind, like the rows; each pulsar's summary.npz (the keys of PTABlockGibbs's) is rewritten
-    from them and kept as ``summary`` on its sampler.  b is recorded as in the default mode."""
+    from them and kept as ``summary`` on its sampler.  b is recorded as in the default mode.
+    acf_lags = L > 0: gs_chain_acf_block follows the summary kernel behind each block, each
+    pulsar's pooled autocovariance up to lag L rides in a third extra buffer, and summary.npz gains
+    acf_lags, acov, iat, iat_window, ess_per_sweep, ess and ess_se (diagnostics.acf_summary; the
+    O(n_f L) window search stays on the host).  With acf_lags 0 nothing is added or launched."""
     P = len(samplers)
     nc = samplers[0].nchains
     ctx = model.ctx
@@ -215,12 +225,14 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     else:
         # x rows into HBM slots: the summary kernel reads them there, and the copy engine takes
         # the first K chains of each pulsar; the reduced arrays of a save point ride in two more
-        # buffers of the slot (a leading axis of 1: the streamer slices rows)
+        # buffers of the slot, three with acf_lags (a leading axis of 1: the streamer slices rows)
         lo, hi = flat_bounds(samplers[0].params)
-        summ = ChainSummary(ctx, nc, n_f, lo, hi, n_bins=summary[0], burn=summary[1], n_group=P)
-        streamer = HistoryStreamer(ctx, shapes + [(1,) + tuple(e) for e in summ.extra_shapes],
-                                   views=[lambda t: t.view(t.shape[0], P, nc, n_f)[:, :, :K], None, None, None],
-                                   direct=[False, not allb, False, False])
+        summ = ChainSummary(ctx, nc, n_f, lo, hi, n_bins=summary[0], burn=summary[1], n_group=P,
+                            acf_lags=summary[3])
+        extra = [(1,) + tuple(e) for e in summ.extra_shapes]
+        keep = lambda t: t.view(t.shape[0], P, nc, n_f)[:, :, :K]   # noqa: E731
+        streamer = HistoryStreamer(ctx, shapes + extra, views=[keep, None] + [None] * len(extra),
+                                   direct=[False, not allb] + [False] * len(extra))
         for s in samplers:
             s.summary = None
     bstride = bk
@@ -250,12 +262,15 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
         save = last % save_every == 0 and last > 0
         if summ is not None and (save or nxt == niter):
             # rows [burn, last] of every chain, reduced on the device behind the block
-            red = summ.unpack(sum_h[0][0], sum_h[1][0])
+            red = summ.unpack(*[h[0] for h in sum_h])
+            acov = red.pop("acov", None)
             for p, (s, o) in enumerate(zip(samplers, outdirs)):
                 s.summary = dict(names=np.array(s.param_names), lo=summ.lo_host, hi=summ.hi_host,
                                  n_bins=np.int64(summ.n_bins), burn=np.int64(summ.burn), nchains=np.int64(nc),
                                  rows=np.int64(nxt),
                                  **{k: v if P == 1 or k == "n" else v[p].copy() for k, v in red.items()})
+                if acov is not None:
+                    s.summary.update(acf_summary(acov if P == 1 else acov[p].copy(), int(red["n"]), nc))
                 s._write_summary(o, s.summary)
         for p, (s, o) in enumerate(zip(samplers, outdirs)):
             xp = xh[:, p]
@@ -280,7 +295,7 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
             summ.accumulate_block(xr, ii, n)
             if ((nxt - 1) % save_every == 0 and nxt > 1) or nxt == niter:
                 # reduced on the side stream, in front of the slot's copies and beside the next block
-                summ.pack_behind(streamer.side, sum_d[0][0], sum_d[1][0])
+                summ.pack_behind(streamer.side, *[d[0] for d in sum_d])
         with torch.cuda.stream(ctx.stream):
             fc_host[slot].copy_(runner.fail_count, non_blocking=True)
             info_host[slot].copy_(runner.info, non_blocking=True)
@@ -811,7 +826,7 @@ class PulsarBlockGibbs(object):
             raise NotImplementedError("gw rho parameters must be the whole parameter vector")
 
     def sample(self, xs, outdir="./", niter=10000, resume=False, save_every=100, *, flush_final=False,
-               record_bchains=None, history="memory", bins=None, burn=None, record_chains=None):
+               record_bchains=None, history="memory", bins=None, burn=None, record_chains=None, acf_lags=None):
         """PulsarBlockGibbs.sample (pulsar_gibbs.py:620-710) as persistent device sweeps.
 
         Chain row ii holds the state BEFORE sweep ii (row 0 = xs, bchain[0] = 0).
@@ -832,8 +847,21 @@ class PulsarBlockGibbs(object):
         ``record_chains`` to 1; given with any other history they raise ValueError.  Files the mode
         does not write are left alone: a chains.npy that an earlier run left in ``outdir`` stays
         beside the new summary.npz when record_chains is 1.  resume=True is not wired for this
-        mode."""
-        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume)
+        mode.
+
+        acf_lags=L (only with history="summary"; an integer in 1..min(4096, niter - burn - 1)): the
+        device also accumulates the autocovariance of every parameter pooled over all chains up to
+        lag L (gs_chain_acf_block behind each block; the estimator of diagnostics.pooled_iat,
+        restated on the host as diagnostics.acov_chains), and summary.npz / ``self.summary`` gain
+        ``acf_lags``, ``acov`` (n_param, L + 1), ``iat`` and ``iat_window`` (Sokal's window within L;
+        -1 where L was too short, and ``iat`` then is the lower bound tau(L)), ``ess_per_sweep`` =
+        1 / iat, ``ess`` = nchains n / iat and ``ess_se`` (Sokal's asymptotic term; NaN where the
+        window was not reached).  Without the keyword the mode's files, launches and bits are
+        unchanged.  Not covered: PTABlockGibbs (its summary is accumulated per sweep from the live
+        state: there is no block of all chains' rows), the red, ECORR and white sample loops,
+        resume, and the spread over groups of chains that diagnostics.ess_table adds to the
+        error."""
+        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume, acf_lags)
         self._check_device_loop(xs)
         if summary is not None and (self._red_loop() or self._ecorr_loop() or self._white_loop()):
             raise NotImplementedError(

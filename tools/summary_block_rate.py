@@ -12,7 +12,11 @@
                                                   point's finalize / pack into the slot's two extra
                                                   buffers on the side stream, chain 0's x and the
                                                   extras copied behind the block), C0 the same without
-                                                  finalize / pack
+                                                  finalize / pack; with --acf-lags L also CL, C with
+                                                  acf_lags=L (gs_chain_acf_block behind the summary
+                                                  kernel, gs_chain_acf_reduce and acov in a third
+                                                  extra buffer), beside the kernel's FMA floor at the
+                                                  FP64 vector roof bench.py uses
     python tools/summary_block_rate.py sample --history memory|summary [--nchains N --niter N]
                                                   PulsarBlockGibbs.sample end to end in this process:
                                                   wall time, chain-it/s and peak host memory (ru_maxrss)
@@ -33,6 +37,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 NF, S = 30, 100
+FP64_PEAK_TFLOPS = 78.6                            # bench.py's FP64 vector roof of the MI355X
 
 
 def event_ms(stream, fn, n):
@@ -136,16 +141,36 @@ def block(a):
             summ.accumulate_block(xs, run.it - S, S)
             summ.pack_behind(hbm.side, extra[0][0], extra[1][0])
         streamed(hbm, after)
-    t = {"A": [], "B": [], "C0": [], "C": []}
-    for fn in (run_a, run_b, run_c0, run_c):
+    legs = [("A", run_a), ("B", run_b), ("C0", run_c0), ("C", run_c)]
+    acf = {}
+    if a.acf_lags:
+        # CL: C with acf_lags -- its own summary (the ACF state) and a slot with the third buffer
+        summ_l = ChainSummary(ctx, C, NF, np.full(NF, -9.0), np.full(NF, -4.0), n_bins=a.bins, acf_lags=a.acf_lags)
+        hbm_l = HistoryStreamer(ctx, shapes + [(1,) + tuple(e) for e in summ_l.extra_shapes],
+                                views=[keep, None, None, None, None], direct=[False, True, False, False, False])
+
+        def run_cl():
+            def after(xs, extra):
+                summ_l.accumulate_block(xs, run.it - S, S)
+                summ_l.pack_behind(hbm_l.side, *[e[0] for e in extra])
+            streamed(hbm_l, after)
+        legs.append(("CL", run_cl))
+    t = {k: [] for k, _ in legs}
+    for _, fn in legs:
         state["pending"] = None
         fn(), fn()                                 # warm every shape the timed window uses
-    for _ in range(a.rounds):                      # alternate the three
-        for k, fn in (("A", run_a), ("B", run_b), ("C0", run_c0), ("C", run_c)):
+    for _ in range(a.rounds):                      # alternate the legs
+        for k, fn in legs:
             state["pending"] = None
             t[k].append(event_ms(ctx.stream, fn, a.blocks))
     best = {k: min(v) for k, v in t.items()}
-    print(json.dumps(dict(mode="block", nchains=C, blocks=a.blocks, bins=a.bins,
+    if a.acf_lags:
+        fma = C * NF * S * (a.acf_lags + 1)        # (L + 1) per recorded value
+        acf = dict(acf_lags=a.acf_lags, CL_minus_C_us=round((best["CL"] - best["C"]) * 1e3, 1),
+                   C_spread_us=round((max(t["C"]) - min(t["C"])) * 1e3, 1), acf_fma=fma,
+                   acf_fma_floor_us=round(fma / (FP64_PEAK_TFLOPS / 2 * 1e12) * 1e6, 1),
+                   acf_state_MB=round(summ_l.acf_state.numel() * 8 / 1e6, 1))
+    print(json.dumps(dict(mode="block", nchains=C, blocks=a.blocks, bins=a.bins, **acf,
                           ms={k: [round(x, 4) for x in v] for k, v in t.items()},
                           C_minus_A_us=round((best["C"] - best["A"]) * 1e3, 1),
                           C0_minus_A_us=round((best["C0"] - best["A"]) * 1e3, 1),
@@ -159,6 +184,8 @@ def sample(a):
     gb = PulsarBlockGibbs(pta, nchains=a.nchains, seed=1)
     x0 = np.random.default_rng(0).uniform(-9, -4, NF)
     kw = dict(history="summary", bins=a.bins) if a.history == "summary" else {}
+    if a.acf_lags:
+        kw["acf_lags"] = a.acf_lags
     with tempfile.TemporaryDirectory() as d:
         gb.sample(x0, outdir=d, niter=1 + S, **kw)                       # warm-up: code objects, pinned slots
         torch.cuda.synchronize()
@@ -180,6 +207,7 @@ def main():
     p.add_argument("--nchains", type=int, default=4096)
     p.add_argument("--niter", type=int, default=5001)
     p.add_argument("--history", choices=("memory", "summary"), default="summary")
+    p.add_argument("--acf-lags", type=int, default=0, help="block: also time C with acf_lags=L; sample: pass it on")
     a = p.parse_args()
     if not torch.cuda.is_available():
         sys.exit("summary_block_rate.py measures on the GPU: none is visible")
