@@ -516,6 +516,51 @@ int gs_chain_acf_block(gs_ctx* ctx, int n_group, int n_chain, int n_param, const
                        double* state);
 int gs_chain_acf_reduce(gs_ctx* ctx, int n_group, int n_chain, int n_param, int max_lag, const double* state,
                         double* acov, int64_t* n);
+/*
+ * Pooled first and second moments of the recorded coefficients b of a block layout -- what
+ * sample(history="summary", b_moments=True) of the single-pulsar samplers reports.  For one group
+ * (a pulsar with m[g] coefficients) over its N = n_chain x (post-burn rows) samples v,
+ *   mean[i] = 1 / N sum v_i,   cov[i][k] = 1 / N sum (v_i - mean[i])(v_k - mean[k]),   i, k < m[g]:
+ * pooled over chains and rows, ddof 0 -- restated on the host as diagnostics.coef_moments.  Mean
+ * and sd of any linear function of b (the delay T_cols b_cols at every TOA:
+ * diagnostics.reconstruct) follow from them.
+ *
+ * gs_coef_moments_state_size: the doubles of one opaque state buffer for these shapes (-1 for
+ * shapes the entries reject).  All zeros means empty.  The layout belongs to the library: per
+ * group the sample count n, shift[ldb], and each workgroup's own partials of S1[i] = sum d_i and
+ * S2[i][k] = sum d_i d_k, d = v - shift, as the lower triangle of 16 x 16 tiles.
+ *
+ * gs_coef_moments_block adds one block of rows; layout, row_stride, burn and the sweep counter are
+ * gs_chain_summary_block's with ldb in place of n_param: v(r, g, c, i) = b[r * row_stride + (g *
+ * n_chain + c) * ldb + i] for i < m[g], m a device int32 [n_group] with entries in 1..ldb (the
+ * same in every call on one state); row r belongs to sweep `sweep + r` (+ the attached counter)
+ * and is skipped below `burn`.  Columns i >= m[g] and the padding of a row are never read into a
+ * result.  An empty group that gets a post-burn row takes chain 0's values of that row as its
+ * shift (timing-model coefficients can sit many standard deviations from zero: without the shift
+ * the covariance cancels).  Two or three launches: the shift and the count, then the products by
+ * v_mfma_f64_16x16x4_f64 -- a workgroup owns a fixed strip of one group's chains and the tiles of
+ * up to 5 x 5 column blocks; a step is 4 consecutive chains of a row, one register per column
+ * block serves as the A operand of its tile row and the B operand of its tile column (15 tile
+ * products from 5 loads at ldb = 76); the waves of a workgroup are added in a fixed order onto the
+ * workgroup's own partial.  ldb > 80 adds a launch for the tiles between different sets of 5
+ * column blocks.
+ *
+ * gs_coef_moments_reduce adds the partials in ascending order and writes n [n_group], shift and
+ * mean = shift + S1 / n [n_group x ldb], and cov = S2 / n - S1 S1^T / n^2 [n_group x ldb x ldb],
+ * exactly symmetric, both triangles filled; entries beyond m[g] are zero, a group with n = 0 has
+ * NaN mean and cov.  It does not modify `state`: save points may call it repeatedly.
+ *
+ * No floating-point atomics: the order of every sum depends on the shapes and the call sequence
+ * only, so every result is reproducible run to run.  A non-finite value makes its own group's
+ * mean and cov NaN and leaves every other group correct.
+ * n_group >= 0, n_chain >= 0, n_rows >= 0, 1 <= ldb <= 512, row_stride >= n_group * n_chain * ldb,
+ * n_rows * n_group * n_chain < 2^31, n_group * ldb < 2^30.  Calls with no work launch nothing.
+ */
+int64_t gs_coef_moments_state_size(int n_group, int n_chain, int ldb);
+int gs_coef_moments_block(gs_ctx* ctx, int n_group, int n_chain, int ldb, const int32_t* m, const double* b,
+                          int n_rows, int64_t row_stride, int64_t sweep, int64_t burn, double* state);
+int gs_coef_moments_reduce(gs_ctx* ctx, int n_group, int n_chain, int ldb, const int32_t* m, const double* state,
+                           int64_t* n, double* shift, double* mean, double* cov);
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate);

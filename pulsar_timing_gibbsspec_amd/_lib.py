@@ -84,6 +84,9 @@ SIGNATURES = {
     "gs_chain_acf_state_size": (_I64, [_I, _I, _I, _I]),
     "gs_chain_acf_block": (_I, [_P, _I, _I, _I, _P, _I, _I64, _I64, _I64, _I, _P, _P]),
     "gs_chain_acf_reduce": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "gs_coef_moments_state_size": (_I64, [_I, _I, _I]),
+    "gs_coef_moments_block": (_I, [_P, _I, _I, _I, _P, _P, _I, _I64, _I64, _I64, _P]),
+    "gs_coef_moments_reduce": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gs_pta_gate_phiinv": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gs_pta_gate_phiinv_irn": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "gs_phi_powerlaw": (_I, [_P, _I, _I, _I, _P, _I, _P, _P, _P]),

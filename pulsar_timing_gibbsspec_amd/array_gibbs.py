@@ -100,7 +100,7 @@ class PulsarArrayGibbs(object):
         return DeviceModel(self.ctx, T, N, R, [s.gwid for s in self.samplers], fixed)
 
     def sample(self, xs_list, outdir="./", niter=10000, resume=False, save_every=100, record_bchains=None, *,
-               history="memory", bins=None, burn=None, record_chains=None, acf_lags=None):
+               history="memory", bins=None, burn=None, record_chains=None, acf_lags=None, b_moments=False):
         """Every pulsar's PulsarBlockGibbs.sample (pulsar_gibbs.py:620-710) at once.
         xs_list[p]: pulsar p's initial parameter vector.  Pulsar p writes to
         ``outdir/<pulsar name>/``.  Returns the list of chain-0 chains.
@@ -111,10 +111,14 @@ class PulsarArrayGibbs(object):
         ``samplers[p].summary`` holds it; record_chains chains of each pulsar reach the host.
         acf_lags=L: as PulsarBlockGibbs.sample -- each pulsar's summary also holds its own pooled
         autocovariance up to lag L with the IAT and ESS of every parameter (gs_chain_acf_block, one
-        group per pulsar; resume and the spread over groups of chains are not covered)."""
+        group per pulsar; resume and the spread over groups of chains are not covered).
+        b_moments=True: as PulsarBlockGibbs.sample -- each pulsar's summary also holds the pooled mean
+        and covariance of its own coefficients over all its chains, b_names, b_n, b_shift, b_mean
+        and b_cov (gs_coef_moments_block, one group of m[p] coefficients per pulsar)."""
         if len(xs_list) != len(self.samplers):
             raise ValueError(f"{len(xs_list)} initial vectors for {len(self.samplers)} pulsars")
-        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume, acf_lags)
+        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume, acf_lags,
+                                    b_moments)
         if summary is not None:
             lo, hi = flat_bounds(self.samplers[0].params)
             for s in self.samplers[1:]:

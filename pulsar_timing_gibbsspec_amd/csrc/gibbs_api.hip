@@ -893,6 +893,64 @@ int gs_chain_acf_reduce(gs_ctx* ctx, int n_group, int n_chain, int n_param, int 
   return after_launch("k_chain_acf_finish");
 }
 
+// the shape arguments the gs_coef_moments_* entries share; 0 or the failing argument's index
+static int bmom_shape(int n_group, int n_chain, int ldb) {
+  if (n_group < 0) return fail_arg(2, "n_group must be >= 0");
+  if (n_chain < 0) return fail_arg(3, "n_chain must be >= 0");
+  if (ldb < 1 || ldb > 512) return fail_arg(4, "ldb must be in 1..512");
+  // launch grids: n_group * ldb blocks of the reduction, and of the product kernel at most 512 + one
+  // workgroup per group and pair of column sets (28 pairs at ldb = 512)
+  if ((int64_t)n_group * ldb > 0x3fffffffLL) return fail_arg(2, "n_group * ldb must be below 2^30");
+  return 0;
+}
+
+int64_t gs_coef_moments_state_size(int n_group, int n_chain, int ldb) {
+  if (n_group < 0 || n_chain < 0 || ldb < 1 || ldb > 512 || (int64_t)n_group * ldb > 0x3fffffffLL) return -1;
+  return bmom_plan(n_group, n_chain, ldb).size;
+}
+
+int gs_coef_moments_block(gs_ctx* ctx, int n_group, int n_chain, int ldb, const int32_t* m, const double* b,
+                          int n_rows, int64_t row_stride, int64_t sweep, int64_t burn, double* state) {
+  if (!ctx) return fail_arg(1, "ctx is NULL");
+  if (int rc = bmom_shape(n_group, n_chain, ldb)) return rc;
+  if (!m) return fail_arg(5, "m is NULL");
+  if (!b) return fail_arg(6, "b is NULL");
+  if (n_rows < 0) return fail_arg(7, "n_rows must be >= 0");
+  if ((__int128)n_rows * n_group * n_chain > 0x7fffffffLL)
+    return fail_arg(7, "n_rows * n_group * n_chain must be below 2^31");
+  if ((__int128)row_stride < (__int128)n_group * n_chain * ldb)
+    return fail_arg(8, "row_stride must be >= n_group * n_chain * ldb");
+  if (!state) return fail_arg(11, "state is NULL");
+  if (n_group == 0 || n_chain == 0 || n_rows == 0) return 0;
+  BmomArgs a;
+  a.n_group = n_group; a.n_chain = n_chain; a.ldb = ldb; a.n_rows = n_rows;
+  a.row_stride = row_stride; a.sweep = sweep; a.burn = burn; a.sweep_dev = ctx->sweep_dev;
+  a.m = m; a.b = b; a.state = state;
+  a.plan = bmom_plan(n_group, n_chain, ldb);
+  launch_coef_moments_block(ctx->stream, a);
+  return after_launch("k_coef_moments_block");
+}
+
+int gs_coef_moments_reduce(gs_ctx* ctx, int n_group, int n_chain, int ldb, const int32_t* m, const double* state,
+                           int64_t* n, double* shift, double* mean, double* cov) {
+  if (!ctx) return fail_arg(1, "ctx is NULL");
+  if (int rc = bmom_shape(n_group, n_chain, ldb)) return rc;
+  if (!m) return fail_arg(5, "m is NULL");
+  if (!state) return fail_arg(6, "state is NULL");
+  if (!n) return fail_arg(7, "n is NULL");
+  if (!shift) return fail_arg(8, "shift is NULL");
+  if (!mean) return fail_arg(9, "mean is NULL");
+  if (!cov) return fail_arg(10, "cov is NULL");
+  if (n_group == 0) return 0;
+  BmomArgs a;
+  a.n_group = n_group; a.n_chain = n_chain; a.ldb = ldb; a.n_rows = 0;
+  a.row_stride = 0; a.sweep = 0; a.burn = 0; a.sweep_dev = nullptr;
+  a.m = m; a.b = nullptr; a.state = const_cast<double*>(state);
+  a.plan = bmom_plan(n_group, n_chain, ldb);
+  launch_coef_moments_reduce(ctx->stream, a, n, shift, mean, cov);
+  return after_launch("k_coef_moments_reduce");
+}
+
 int gs_pta_gate_phiinv(gs_ctx* ctx, int n_psr, int n_chain, int n_f, int n_param, const double* x,
                        const double* xlast, const int32_t* gw_col, const int32_t* red_col,
                        double* phiinv_F, int32_t* gate) {

@@ -298,6 +298,25 @@ struct AcfArgs {
 };
 int launch_chain_acf_block(hipStream_t s, AcfArgs a);
 int launch_chain_acf_reduce(hipStream_t s, AcfArgs a, double* acov, int64_t* n);
+struct BmomPlan {  // gs_coef_moments_* (gibbs_bmom.hip): fixed by (n_group, n_chain, ldb) alone
+  int nt;            // 16-column blocks of a row: ceil(ldb / 16)
+  int nsb;           // sets of 5 column blocks: ceil(nt / 5)
+  int noff;          // pairs of different sets: nsb (nsb - 1) / 2
+  int64_t cs, ns;    // chains per workgroup, workgroups (chain strips) per (group, pair of sets)
+  int64_t off_shift, off_diag, off_off, size;  // the state's arrays and its length, in doubles
+};
+BmomPlan bmom_plan(int n_group, int n_chain, int ldb);
+struct BmomArgs {
+  int n_group, n_chain, ldb, n_rows;
+  int64_t row_stride, sweep, burn;
+  const int64_t* sweep_dev;  // ctx sweep counter (graph replay) or NULL
+  const int32_t* m;
+  const double* b;
+  double* state;
+  BmomPlan plan;
+};
+int launch_coef_moments_block(hipStream_t s, BmomArgs a);
+int launch_coef_moments_reduce(hipStream_t s, BmomArgs a, int64_t* n, double* shift, double* mean, double* cov);
 int launch_phi_powerlaw(hipStream_t s, int n_psr, int n_chain, int n_f, const double* x, int ldx,
                         const int32_t* pl_col, const double* lnphi, double* out);
 

@@ -209,6 +209,43 @@ def acf_summary(acov, n, nchains, c=5.0):
                 ess_per_sweep=per, ess=N * per, ess_se=se)
 
 
+def coef_moments(B, shift=None):
+    """Host restatement of the on-device pooled coefficient moments (gs_coef_moments_block /
+    gs_coef_moments_reduce, sample(history="summary", b_moments=True)) for B (chains, n, m), in numpy
+    long double: with d = B - shift over the N = chains x n samples,
+      mean = shift + sum d / N,   cov = sum d d^T / N - (sum d)(sum d)^T / N^2   (pooled, ddof 0).
+    shift (m,): the device's rule when none is given -- chain 0's first row.  Returns a dict of n
+    (int64), shift, mean (m,) and cov (m, m) as doubles; NaN mean and cov for N = 0."""
+    B = np.asarray(B, float)
+    C, n, m = B.shape
+    N = C * n
+    if shift is None:
+        shift = B[0, 0] if N else np.zeros(m)
+    shift = np.asarray(shift, float).reshape(m)
+    if N == 0:
+        return dict(n=np.int64(0), shift=shift, mean=np.full(m, np.nan), cov=np.full((m, m), np.nan))
+    d = B.reshape(N, m).astype(np.longdouble) - shift.astype(np.longdouble)
+    s1 = d.sum(axis=0)
+    s2 = d.T @ d
+    Nl = np.longdouble(N)
+    mean = shift.astype(np.longdouble) + s1 / Nl
+    cov = s2 / Nl - np.outer(s1, s1) / (Nl * Nl)
+    return dict(n=np.int64(N), shift=shift, mean=np.asarray(mean, float), cov=np.asarray(cov, float))
+
+
+def reconstruct(T, mean, cov, cols=None):
+    """Posterior mean and sd, at every TOA, of the delay carried by the columns ``cols`` of the
+    basis T (n_toa, m) -- e.g. a pulsar's Fourier columns -- from the pooled moments of b (a
+    summary.npz's b_mean, b_cov; coef_moments): (T_c mean_c, sqrt(diag(T_c cov_cc T_c^T))), the
+    diagonal taken row by row without forming the n_toa x n_toa matrix.  cols=None: every column."""
+    T = np.asarray(T, float)
+    mean, cov = np.asarray(mean, float), np.asarray(cov, float)
+    cols = np.arange(T.shape[1]) if cols is None else np.asarray(cols, dtype=np.int64).ravel()
+    Tc = T[:, cols]
+    var = np.einsum("ti,ti->t", Tc @ cov[np.ix_(cols, cols)], Tc)
+    return Tc @ mean[cols], np.sqrt(np.maximum(var, 0.0))
+
+
 def hist_quantiles(counts, lo, hi, q):
     """Quantile(s) q of histograms counts (k, n_bins) over [lo, hi] (k,), e.g. a summary.npz's: linear
     interpolation inside the bin where the cumulative count crosses q x total (the first non-empty

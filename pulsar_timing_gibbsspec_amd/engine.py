@@ -643,6 +643,110 @@ class ChainSummary:
         return out
 
 
+class CoefMoments:
+    """Pooled mean and covariance of the recorded coefficients b of every chain, accumulated on the
+    device (gs_coef_moments_block): one group per entry of ``m`` (a pulsar with m[g] <= ldb
+    coefficients), ``n_chain`` chains each.  ``accumulate_block`` takes a block of recorded b rows;
+    sweeps below ``burn`` are skipped on the device.  ``finalize()`` reduces the state
+    (gs_coef_moments_reduce, which leaves it untouched) into n (n_group,), shift, mean
+    (n_group, ldb) and cov (n_group, ldb, ldb) -- diagnostics.coef_moments restates them on the
+    host; entries beyond m[g] are zero.  pack / pack_behind / unpack carry a save point's arrays in
+    three buffers of ``extra_shapes``, as ChainSummary's do."""
+
+    def __init__(self, ctx, n_chain, m, ldb, burn=0):
+        self.ctx, self.n_chain, self.ldb, self.burn = ctx, int(n_chain), int(ldb), int(burn)
+        self.m_host = np.asarray(m, dtype=np.int64).ravel()
+        self.n_group = int(self.m_host.size)
+        if self.n_group < 1:
+            raise ValueError("m must hold one entry per group")
+        if not 1 <= self.ldb <= 512:
+            raise ValueError(f"ldb must be in 1..512 (got {ldb})")
+        if self.m_host.min() < 1 or self.m_host.max() > self.ldb:
+            raise ValueError(f"every m[g] must be in 1..{self.ldb} (got {self.m_host.tolist()})")
+        size = int(ctx.lib.gs_coef_moments_state_size(self.n_group, self.n_chain, self.ldb))
+        if size < 0:
+            raise ValueError(f"gs_coef_moments_state_size rejected {self.n_group} x {self.n_chain} x {self.ldb}")
+        dev = ctx.device
+        k = self.n_group * self.ldb
+        self.m = _t(self.m_host, torch.int32, dev)
+        self.state = torch.zeros(size, dtype=torch.float64, device=dev)             # all zeros: empty
+        self.n = torch.zeros(self.n_group, dtype=torch.int64, device=dev)
+        self.shift_mean = torch.zeros(2, k, dtype=torch.float64, device=dev)
+        self.cov = torch.zeros(k * self.ldb, dtype=torch.float64, device=dev)
+        self._packed = None                        # event of a pack_behind the next accumulation waits for
+
+    def accumulate_block(self, b_block, first_sweep, n_rows):
+        """Add rows [:n_rows] of b_block (rows, n_group * n_chain, ldb), the coefficients before
+        sweeps first_sweep, first_sweep + 1, ...: queued on the context's stream.  The rows may be
+        padded (any row stride >= a row); inside a row the block must be contiguous."""
+        if b_block.dim() != 3 or tuple(b_block.shape[1:]) != (self.n_group * self.n_chain, self.ldb):
+            raise ValueError(f"the moments hold {self.n_group} x {self.n_chain} chains of {self.ldb} "
+                             f"coefficients, the block is {tuple(b_block.shape)}")
+        if b_block.dtype != torch.float64 or b_block.device != self.state.device:
+            raise ValueError(f"the block must be float64 on {self.state.device} (got {b_block.dtype} on "
+                             f"{b_block.device})")
+        row = self.n_group * self.n_chain * self.ldb
+        if not b_block[:1].is_contiguous() or (b_block.shape[0] > 1 and b_block.stride(0) < row):
+            raise ValueError(f"the block's rows must be contiguous and at least {row} apart (strides "
+                             f"{tuple(b_block.stride())})")
+        if not 0 <= int(n_rows) <= b_block.shape[0]:
+            raise ValueError(f"n_rows = {n_rows} of a block of {b_block.shape[0]} rows")
+        if self._packed is not None:
+            self.ctx.stream.wait_event(self._packed)
+            self._packed = None
+        check(self.ctx.lib.gs_coef_moments_block(
+            self.ctx.handle, self.n_group, self.n_chain, self.ldb, ptr(self.m), ptr(b_block[:1]), int(n_rows),
+            max(int(b_block.stride(0)), row), int(first_sweep), self.burn, ptr(self.state)),
+            "gs_coef_moments_block")
+
+    # the three buffers a HistoryStreamer carries for the moments: n (int64 words as float64 bit
+    # patterns), [shift, mean] and cov
+    @property
+    def extra_shapes(self):
+        k = self.n_group * self.ldb
+        return [(self.n_group,), (2, k), (k * self.ldb,)]
+
+    def pack(self, ints, reals, cov, stream=None):
+        """gs_coef_moments_reduce into three float64 buffers of ``extra_shapes`` (a streamer
+        slot's), queued on ``stream`` (default: the context's).  The state is read only."""
+        main = self.ctx.stream
+        other = stream is not None and stream is not main
+        if other:
+            self.ctx.set_stream(stream)
+        try:
+            check(self.ctx.lib.gs_coef_moments_reduce(
+                self.ctx.handle, self.n_group, self.n_chain, self.ldb, ptr(self.m), ptr(self.state),
+                ptr(ints), ptr(reals[0]), ptr(reals[1]), ptr(cov)), "gs_coef_moments_reduce")
+        finally:
+            if other:
+                self.ctx.set_stream(main)
+
+    def finalize(self, stream=None):
+        """Device tensors n, shift, mean, cov (the class's own buffers).  No host synchronisation."""
+        self.pack(self.n.view(torch.float64), self.shift_mean, self.cov, stream=stream)
+        G, ldb = self.n_group, self.ldb
+        return dict(n=self.n, shift=self.shift_mean[0].view(G, ldb), mean=self.shift_mean[1].view(G, ldb),
+                    cov=self.cov.view(G, ldb, ldb))
+
+    def pack_behind(self, stream, ints, reals, cov):
+        """``pack`` on another stream (a streamer's side stream), ordered after what the context's
+        stream holds so far; the next accumulate_block waits for it."""
+        ready = torch.cuda.Event()
+        ready.record(self.ctx.stream)
+        stream.wait_event(ready)
+        self.pack(ints, reals, cov, stream=stream)
+        self._packed = torch.cuda.Event()
+        self._packed.record(stream)
+
+    def unpack(self, ints, reals, cov):
+        """Host arrays of what ``pack`` wrote (the fetched host tensors), a leading group axis on
+        each: n (G,) int64, shift, mean (G, ldb), cov (G, ldb, ldb)."""
+        G, ldb = self.n_group, self.ldb
+        r = reals.numpy()
+        return dict(n=ints.numpy().view(np.int64).copy(), shift=r[0].reshape(G, ldb).copy(),
+                    mean=r[1].reshape(G, ldb).copy(), cov=cov.numpy().reshape(G, ldb, ldb).copy())
+
+
 def grid3(rhomin, rhomax, n=1000, device="cuda"):
     """[rho_g | log rho_g | 0.5 log10 rho_g], rho_g = 10**linspace(log10 rhomin, log10 rhomax, n)
     — numpy on the host, so the device sees the reference's exact grid

@@ -41,7 +41,7 @@ import torch
 from . import _lib
 from .diagnostics import acf_summary, white_aclength
 from .ecorr import EcorrFreeSpectrumChains, EcorrModel, EcorrWhiteChains
-from .engine import ChainSummary, DeviceModel, FreeSpectrumChains, HistoryStreamer, check_handoff, grid3
+from .engine import ChainSummary, CoefMoments, DeviceModel, FreeSpectrumChains, HistoryStreamer, check_handoff, grid3
 from .plumbing import (basis_layout, expand_names, flat_bounds, last_match, matching_indices, power_bounds,
                        uniform_bounds, vector_to_dict)
 from .rednoise import (DE_BUFFER, RED_STEPS, RedJumps, RedNoiseChains, powerlaw_loglinear,
@@ -86,15 +86,19 @@ def write_summary(outdir, summary):
     os.replace(tmp, f"{outdir}/summary.npz")
 
 
-def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume, acf_lags=None):
-    """The history / bins / burn / record_chains / acf_lags keywords of the single-pulsar samplers,
-    checked before anything is touched: None for history="memory", (bins, burn, record_chains,
-    acf_lags) for history="summary" (acf_lags 0 when it was not given)."""
+def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume, acf_lags=None, b_moments=False):
+    """The history / bins / burn / record_chains / acf_lags / b_moments keywords of the
+    single-pulsar samplers, checked before anything is touched: None for history="memory", (bins,
+    burn, record_chains, acf_lags, b_moments) for history="summary" (acf_lags 0 when it was not
+    given)."""
     if history not in ("memory", "summary"):
         raise ValueError("history must be 'memory' or 'summary'")
+    if not isinstance(b_moments, (bool, np.bool_)):
+        raise ValueError(f"b_moments must be a bool (got {b_moments!r})")
     if history != "summary":
-        if bins is not None or burn is not None or record_chains is not None or acf_lags is not None:
-            raise ValueError("bins, burn, record_chains and acf_lags need history='summary'")
+        if (bins is not None or burn is not None or record_chains is not None or acf_lags is not None
+                or b_moments):
+            raise ValueError("bins, burn, record_chains, acf_lags and b_moments need history='summary'")
         return None
     bins = 64 if bins is None else bins
     burn = 0 if burn is None else burn
@@ -112,7 +116,7 @@ def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume
     if resume:
         raise NotImplementedError("resume=True is not wired for history='summary' (the accumulators are "
                                   "not saved)")
-    return int(bins), int(burn), int(K), int(acf_lags or 0)
+    return int(bins), int(burn), int(K), int(acf_lags or 0), bool(b_moments)
 
 
 def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_every, psr_base=0,
@@ -134,7 +138,7 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     b (the reference's bchain) is what the reference layout needs.  Without it only chain 0's
     b rows cross PCIe (the rest are recorded in HBM only).
 
-    summary = (bins, burn, record_chains, acf_lags): history="summary".  The x rows of a block are recorded
+    summary = (bins, burn, record_chains, acf_lags, b_moments): history="summary".  The x rows of a block are recorded
     into HBM slots; only chains 0..record_chains-1 of each pulsar go to the host (``chains`` is
     (record_chains, niter, n_f), or None for one chain -- the (nchains, niter, n_f) array is never
     allocated), and every chain's posterior is accumulated on the device behind each block
@@ -146,7 +150,13 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     acf_lags = L > 0: gs_chain_acf_block follows the summary kernel behind each block, each
     pulsar's pooled autocovariance up to lag L rides in a third extra buffer, and summary.npz gains
     acf_lags, acov, iat, iat_window, ess_per_sweep, ess and ess_se (diagnostics.acf_summary; the
-    O(n_f L) window search stays on the host).  With acf_lags 0 nothing is added or launched."""
+    O(n_f L) window search stays on the host).  With acf_lags 0 nothing is added or launched.
+    b_moments (summary[4]): every chain's b rows are recorded into the slot's HBM buffer
+    (record_b_chains = nchains, never direct) and the streamer's view sends only the chains the run
+    without the keyword sends; engine.CoefMoments (gs_coef_moments_block, one group per pulsar)
+    follows the x summary behind each block, its reduced arrays ride in three more buffers, and
+    summary.npz gains b_names, b_n, b_shift, b_mean and b_cov (diagnostics.coef_moments).  Without
+    it no buffer, launch or key is added."""
     P = len(samplers)
     nc = samplers[0].nchains
     ctx = model.ctx
@@ -217,7 +227,14 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     # every chain's x rows and chain 0's b rows (GS_OPT_BREC_CHAINS = 1; the reference's bchain)
     # straight into the pinned slots; every chain's b (record_bchains) goes through HBM and the
     # copy engine
-    bk = nc if (allb or nc == 1) else 1
+    bk = bstride = nc if (allb or nc == 1) else 1      # chains of b recorded, and of those sent to the host
+    bmom = bsend = None
+    if summary is not None and summary[4]:
+        # b_moments: every chain's b rows into the slot's HBM buffer, where gs_coef_moments_block
+        # reads them; the copy engine takes the chains per pulsar that the host gets without it
+        bmom = CoefMoments(ctx, nc, m, model.ldb, burn=summary[1])
+        bk = nc
+        bsend = lambda t: t.view(t.shape[0], P, nc, model.ldb)[:, :, :bstride]   # noqa: E731
     shapes = [(blk, P * nc, n_f), (blk, P * bk, model.ldb)]
     summ = None
     if summary is None:
@@ -230,12 +247,14 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
         summ = ChainSummary(ctx, nc, n_f, lo, hi, n_bins=summary[0], burn=summary[1], n_group=P,
                             acf_lags=summary[3])
         extra = [(1,) + tuple(e) for e in summ.extra_shapes]
+        n_sum = len(extra)                         # the summary's buffers; the moments' three follow
+        if bmom is not None:
+            extra += [(1,) + tuple(e) for e in bmom.extra_shapes]
         keep = lambda t: t.view(t.shape[0], P, nc, n_f)[:, :, :K]   # noqa: E731
-        streamer = HistoryStreamer(ctx, shapes + extra, views=[keep, None] + [None] * len(extra),
-                                   direct=[False, not allb] + [False] * len(extra))
+        streamer = HistoryStreamer(ctx, shapes + extra, views=[keep, bsend] + [None] * len(extra),
+                                   direct=[False, not allb and bmom is None] + [False] * len(extra))
         for s in samplers:
             s.summary = None
-    bstride = bk
     # failed (non-PD) draws, surfaced per block as they happen: the kernels keep b and count
     # (gs_ctx_set_fail_counts); each block's counts reach pinned memory behind the block
     fc_host = [torch.zeros(P * nc, dtype=torch.int32, pin_memory=True) for _ in range(2)]
@@ -245,7 +264,7 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
 
     def consume(slot, ii, nxt):
         xh, bh, *sum_h = streamer.fetch(slot)
-        xh, bh = xh.numpy().reshape(nxt - ii, P, K, n_f), bh.numpy()
+        xh, bh = xh.numpy().reshape(nxt - ii, P, K, n_f), bh.numpy().reshape(nxt - ii, P * bstride, model.ldb)
         fc_ev[slot].synchronize()
         # a chain whose hand-off wait expired (info = -1) was not advanced: fail loudly
         check_handoff(info_host[slot])
@@ -262,8 +281,9 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
         save = last % save_every == 0 and last > 0
         if summ is not None and (save or nxt == niter):
             # rows [burn, last] of every chain, reduced on the device behind the block
-            red = summ.unpack(*[h[0] for h in sum_h])
+            red = summ.unpack(*[h[0] for h in sum_h[:n_sum]])
             acov = red.pop("acov", None)
+            bred = bmom.unpack(*[h[0] for h in sum_h[n_sum:]]) if bmom is not None else None
             for p, (s, o) in enumerate(zip(samplers, outdirs)):
                 s.summary = dict(names=np.array(s.param_names), lo=summ.lo_host, hi=summ.hi_host,
                                  n_bins=np.int64(summ.n_bins), burn=np.int64(summ.burn), nchains=np.int64(nc),
@@ -271,6 +291,10 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
                                  **{k: v if P == 1 or k == "n" else v[p].copy() for k, v in red.items()})
                 if acov is not None:
                     s.summary.update(acf_summary(acov if P == 1 else acov[p].copy(), int(red["n"]), nc))
+                if bred is not None:
+                    s.summary.update(b_names=np.array(s.b_param_names), b_n=np.int64(bred["n"][p]),
+                                     b_shift=bred["shift"][p, :m[p]].copy(), b_mean=bred["mean"][p, :m[p]].copy(),
+                                     b_cov=bred["cov"][p, :m[p], :m[p]].copy())
                 s._write_summary(o, s.summary)
         for p, (s, o) in enumerate(zip(samplers, outdirs)):
             xp = xh[:, p]
@@ -293,9 +317,13 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
         runner.run(n, x_rec=xr, b_rec=br, record_b_chains=bk)
         if summ is not None:
             summ.accumulate_block(xr, ii, n)
+            if bmom is not None:
+                bmom.accumulate_block(br, ii, n)
             if ((nxt - 1) % save_every == 0 and nxt > 1) or nxt == niter:
                 # reduced on the side stream, in front of the slot's copies and beside the next block
-                summ.pack_behind(streamer.side, *[d[0] for d in sum_d])
+                summ.pack_behind(streamer.side, *[d[0] for d in sum_d[:n_sum]])
+                if bmom is not None:
+                    bmom.pack_behind(streamer.side, *[d[0] for d in sum_d[n_sum:]])
         with torch.cuda.stream(ctx.stream):
             fc_host[slot].copy_(runner.fail_count, non_blocking=True)
             info_host[slot].copy_(runner.info, non_blocking=True)
@@ -826,7 +854,8 @@ class PulsarBlockGibbs(object):
             raise NotImplementedError("gw rho parameters must be the whole parameter vector")
 
     def sample(self, xs, outdir="./", niter=10000, resume=False, save_every=100, *, flush_final=False,
-               record_bchains=None, history="memory", bins=None, burn=None, record_chains=None, acf_lags=None):
+               record_bchains=None, history="memory", bins=None, burn=None, record_chains=None, acf_lags=None,
+               b_moments=False):
         """PulsarBlockGibbs.sample (pulsar_gibbs.py:620-710) as persistent device sweeps.
 
         Chain row ii holds the state BEFORE sweep ii (row 0 = xs, bchain[0] = 0).
@@ -860,8 +889,22 @@ class PulsarBlockGibbs(object):
         unchanged.  Not covered: PTABlockGibbs (its summary is accumulated per sweep from the live
         state: there is no block of all chains' rows), the red, ECORR and white sample loops,
         resume, and the spread over groups of chains that diagnostics.ess_table adds to the
-        error."""
-        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume, acf_lags)
+        error.
+
+        b_moments=True (only with history="summary"): the device also accumulates the pooled first
+        and second moments of the coefficients b over every chain and every row ii >= ``burn``
+        (gs_coef_moments_block behind each block, an fp64-MFMA rank-K update; restated on the host
+        as diagnostics.coef_moments), and summary.npz / ``self.summary`` gain ``b_names`` (the
+        b_param_names), ``b_n`` (chains x post-burn rows), ``b_shift`` (m,), ``b_mean`` (m,) and
+        ``b_cov`` (m, m), pooled with ddof 0.  Mean and sd at every TOA of the delay any columns of
+        T carry follow on the host (diagnostics.reconstruct).  Row 0 is bchain[0] = 0 as recorded:
+        with burn = 0 it is a sample like any other.  Every chain's b is then recorded in HBM; the
+        host still gets the chains it gets without the keyword, and chain.npy / bchain.npy are
+        unchanged.  Not covered: PTABlockGibbs (its b lives in the tiled per-pulsar layout and no
+        block of it is recorded), resume, the red, ECORR and white sample loops, and per-chain
+        moments of b (an R-hat of coefficients)."""
+        summary = summary_arguments(history, bins, burn, record_chains, niter, self.nchains, resume, acf_lags,
+                                    b_moments)
         self._check_device_loop(xs)
         if summary is not None and (self._red_loop() or self._ecorr_loop() or self._white_loop()):
             raise NotImplementedError(
