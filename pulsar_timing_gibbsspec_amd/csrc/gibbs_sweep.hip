@@ -317,6 +317,33 @@ constexpr int GS_PAIR_SCR = SweepPairLds::total;
 #define GS_PAIR_RHO_PRIO 1
 #endif
 
+// The arguments k_sweep_pair's sweep loop reads, fetched where they are used: scalar loads from the
+// kernel-argument segment through an opaque pointer (the loads a use does not need fold away).  Read
+// from the by-value parameter they were loaded once, held in SGPRs across the draw -- spilled into VGPR
+// lanes there -- and brought back at every sweep with a v_readlane_b32 each, a VALU issue slot: 16 at
+// the head of the rho step alone.  GS_PAIR_ARGS_RELOAD = 0 reads the parameter (A/B builds).
+#ifndef GS_PAIR_ARGS_RELOAD
+#define GS_PAIR_ARGS_RELOAD 1
+#endif
+struct PairLoopArgs {
+  int64_t it0;
+  double rhomin, rhomax;
+  double *x_rec, *b_rec;
+  int32_t* fail_count;
+  gs_key key;
+  int psr_base;
+};
+__device__ __forceinline__ PairLoopArgs pair_loop_args(const SweepArgs& A) {
+  if constexpr (GS_PAIR_ARGS_RELOAD != 0) {
+    // (SweepArgs is the kernel's only parameter: it sits at the start of the segment)
+    auto* k = (const __attribute__((address_space(4))) SweepArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(k));
+    return {k->it0, k->rhomin, k->rhomax, k->x_rec, k->b_rec, k->fail_count, {k->key.k0, k->key.k1}, k->psr_base};
+  } else {
+    return {A.it0, A.rhomin, A.rhomax, A.x_rec, A.b_rec, A.fail_count, A.key, A.psr_base};
+  }
+}
+
 template <int WPB>
 __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
   extern __shared__ double lds[];
@@ -374,12 +401,13 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
   }
 #pragma unroll 1
   for (int sw = 0; sw < S; ++sw) {
-    const long long ii = A.it0 + sw;
+    const PairLoopArgs Ah = pair_loop_args(A);
+    const long long ii = Ah.it0 + sw;
 #pragma unroll
     for (int ch = 0; ch < 2; ++ch) {  // record-before-update (pulsar_gibbs.py:658-659)
-      if (xro[ch] >= 0) A.x_rec[sw * xr_step + xro[ch]] = x[ch];
-      if (bFo[ch] >= 0) A.b_rec[sw * br_step + bFo[ch]] = bF[ch];
-      if (bMo[ch] >= 0) A.b_rec[sw * br_step + bMo[ch]] = bM[ch];
+      if (xro[ch] >= 0) Ah.x_rec[sw * xr_step + xro[ch]] = x[ch];
+      if (bFo[ch] >= 0) Ah.b_rec[sw * br_step + bFo[ch]] = bF[ch];
+      if (bMo[ch] >= 0) Ah.b_rec[sw * br_step + bMo[ch]] = bM[ch];
     }
 #pragma unroll 1
     for (int pass = (ii == 0) ? 0 : 1; pass < 2; ++pass) {
@@ -410,10 +438,11 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
           int kc = k;
           uint32_t cz = (uint32_t)(h ? gchain[1] : gchain[0]);  // the counter's chain word
           asm volatile("" : "+v"(kc), "+v"(cz));
-          gs_uniform2(gs_counter(kc, ii, cz, p + A.psr_base, GS_EV_RHO), pair_key(A.key), U, u2);
+          const PairLoopArgs Ar = pair_loop_args(A);
+          gs_uniform2(gs_counter(kc, ii, cz, p + Ar.psr_base, GS_EV_RHO), pair_key(Ar.key), U, u2);
           // (1 - exp(arg) is exactly 1 where the law skips the exp, so its one ballot over both chains
           // draws the same values as a ballot per chain)
-          const RhoDraw rd = rho_given_b(tau, U, A.rhomin, A.rhomax, irhomin, irhomax, am);
+          const RhoDraw rd = rho_given_b(tau, U, Ar.rhomin, Ar.rhomax, irhomin, irhomax, am);
           const double xnew = rd.xnew, phm = rd.phinv;
           // gate: all(xnew != x_old[-1])  (pulsar_gibbs.py:697), per chain
           const double xl0 = rdlane(x[0], NF - 1), xl1 = rdlane(x[1], NF - 1);
@@ -437,13 +466,14 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
         ev = GS_EV_B;
       }
       double zF[2], zM[2];
+      const PairLoopArgs Ad = pair_loop_args(A);
       if (pfv) {
 #pragma unroll
         for (int ch = 0; ch < 2; ++ch) pair_prefetch_read(pfslot, ch, lane, zF[ch], zM[ch]);
       } else {
 #pragma unroll
         for (int ch = 0; ch < 2; ++ch)
-          gs_normal2(gs_counter(lane, ii, gchain[ch], p + A.psr_base, ev), pair_key(A.key), zF[ch], zM[ch]);
+          gs_normal2(gs_counter(lane, ii, gchain[ch], p + Ad.psr_base, ev), pair_key(Ad.key), zF[ch], zM[ch]);
       }
 #pragma unroll
       for (int ch = 0; ch < 2; ++ch) {
@@ -457,8 +487,8 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
       // the draw that follows is GS_EV_B of this sweep (after pass 0) or of the next: same counters,
       // functions and bits as the inline path.  (The last sweep's prefetch is generated and dropped: a
       // uniform branch around it would cut the draw's tail into separate scheduling regions.)
-      const PairPrefetch pf = {A.key, (uint32_t)(ii + pass), {(uint32_t)gchain[0], (uint32_t)gchain[1]},
-                               p + A.psr_base, GS_EV_B, pfslot};
+      const PairPrefetch pf = {Ad.key, (uint32_t)(ii + pass), {(uint32_t)gchain[0], (uint32_t)gchain[1]},
+                               p + Ad.psr_base, GS_EV_B, pfslot};
       bdraw_tile_pair60<true, true>(M, NMXe, nM, lane, phinv, zF, zM, bF, bM, scr, zmslot, f, pf);
       pfv = true;
       gtile::lds_fence();
@@ -473,7 +503,8 @@ __global__ __launch_bounds__(64 * WPB, 2) void k_sweep_pair(SweepArgs A) {
         }
         if (draw[ch] && f[ch]) {
           if (!fail[ch]) fail[ch] = f[ch];
-          if (A.fail_count && lane == 0) A.fail_count[sys[ch]] += 1;
+          int32_t* const fc = pair_loop_args(A).fail_count;
+          if (fc && lane == 0) fc[sys[ch]] += 1;
         }
       }
     }

@@ -153,9 +153,25 @@ __device__ __forceinline__ void tile_elim_pair(double (&A)[8], double (&B)[8], d
       // per step than tile_elim1's row-group granularity.  tile_elim1 also updates the register's other
       // rows of the row group (rows < k of A: eliminated rows nothing reads again; rows > k of B: still
       // identity rows, whose update adds ng x 0 = +-0 and leaves them unchanged for a finite ng), so
-      // every value read afterwards is the same
+      // every value read afterwards is the same.
+      // Two more updates of A are left out because nothing reads their result (r08, 37 fmacs of a pair
+      // draw's 556).  What is read of A after step k: the rn broadcast of row k' + 1 at each later step
+      // k', the diagonal A[c][c] at the end (dg) and, by the caller, row KMAX of a tile with KMAX < 16
+      // (the augmented row CP).
+      //  * odd k: register ptk(k) holds rows k - 1 and k.  Row k - 1 is eliminated; of row k the later
+      //    steps broadcast nothing (they start at row k + 2, in the next register) and the only later
+      //    read is A[k][k].  Step k adds A[k][k] x ng there with ng = -0 in lanes c <= k, which leaves
+      //    a finite A[k][k] as it is; a non-finite one stays non-finite (inf instead of NaN) and is
+      //    the same bad pivot to the ballot, after which the draw is discarded.  So A starts at
+      //    ptk(k) + 1.  (At even k the register also holds row k + 1, whose columns > k this step
+      //    does change: kept.)
+      //  * KMAX < 16: the registers above ptk(KMAX) hold rows > KMAX only -- padding rows.  rn
+      //    stops at row KMAX - 1, dg is overridden by 1 for c >= KMAX, the caller reads row KMAX only
+      //    (register ptk(KMAX)); for KMAX = CP = 12 that is register 7 (rows 14, 15), skipped in
+      //    every step.
+      const int a0 = ptk(k) + (k & 1), a1 = KMAX < 16 ? ptk(KMAX) + 1 : 8;
 #pragma unroll
-      for (int t = ptk(k); t < 8; ++t) A[t] = fmac_nb(A[t], A[t], ng, k);
+      for (int t = a0; t < a1; ++t) A[t] = fmac_nb(A[t], A[t], ng, k);
 #pragma unroll
       for (int t = 0; t <= ptk(k); ++t) B[t] = fmac_nb(B[t], B[t], ng, k);
     }
