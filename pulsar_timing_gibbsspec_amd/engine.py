@@ -9,6 +9,7 @@
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import numpy as np
@@ -16,6 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr
+from .diagnostics import acf_summary
 
 TUNED_NF = (20, 40, 60)          # fixed-NF instantiations (every broadcast variant)
 FUSED_NF_MAX = 64                # register-tile b-draw and the fused sweep: any even NF <= 64
@@ -436,7 +438,63 @@ class BlockRecorder:
             (row or 0) * self.n_param, ptr(self.slots), ptr(self.sel), ptr(eng.xlast)), "gs_pta_record_block")
 
 
-class ChainSummary:
+class _BlockAccumulator:
+    """What ChainSummary and CoefMoments share: the check of a block of recorded rows, a C entry
+    queued on another stream, and the stream order of a save point.  ``pack_behind`` runs ``pack``
+    on a side stream behind what the context's stream holds so far, and the next accumulation
+    waits for it on the device, so the state ``pack`` reads does not move under it."""
+
+    _holds = ("summary holds", "parameters")   # the words of _check_block's shape error
+    _packed = None                             # event of a pack_behind the next accumulation waits for
+
+    def _check_block(self, block, width, n_rows, like):
+        """block: (rows, n_group * n_chain, width) float64 on ``like``'s device; rows may be padded
+        (any row stride >= a row), inside a row the block is contiguous.  Returns the row stride."""
+        if block.dim() != 3 or tuple(block.shape[1:]) != (self.n_group * self.n_chain, width):
+            raise ValueError(f"the {self._holds[0]} {self.n_group} x {self.n_chain} chains of {width} "
+                             f"{self._holds[1]}, the block is {tuple(block.shape)}")
+        if block.dtype != torch.float64 or block.device != like.device:
+            raise ValueError(f"the block must be float64 on {like.device} (got {block.dtype} on "
+                             f"{block.device})")
+        row = self.n_group * self.n_chain * width
+        if not block[:1].is_contiguous() or (block.shape[0] > 1 and block.stride(0) < row):
+            raise ValueError(f"the block's rows must be contiguous and at least {row} apart (strides "
+                             f"{tuple(block.stride())})")
+        if not 0 <= int(n_rows) <= block.shape[0]:
+            raise ValueError(f"n_rows = {n_rows} of a block of {block.shape[0]} rows")
+        return max(int(block.stride(0)), row)
+
+    def _after_pack(self):
+        if self._packed is not None:
+            self.ctx.stream.wait_event(self._packed)
+            self._packed = None
+
+    @contextlib.contextmanager
+    def _queued_on(self, stream):
+        """The context's C entries go to ``stream`` (None: where they go anyway) inside the block."""
+        main = self.ctx.stream
+        other = stream is not None and stream is not main
+        if other:
+            self.ctx.set_stream(stream)
+        try:
+            yield
+        finally:
+            if other:
+                self.ctx.set_stream(main)
+
+    def pack_behind(self, stream, *bufs):
+        """``pack(*bufs)`` on another stream (a streamer's side stream), ordered after what the
+        context's stream holds so far: the reduction then runs beside the next block's sweeps
+        instead of in front of them.  The next accumulation waits for it on the device."""
+        ready = torch.cuda.Event()
+        ready.record(self.ctx.stream)
+        stream.wait_event(ready)
+        self.pack(*bufs, stream=stream)
+        self._packed = torch.cuda.Event()
+        self._packed.record(stream)
+
+
+class ChainSummary(_BlockAccumulator):
     """Posterior summaries of every chain, accumulated on the device (gs_chain_summary): per
     (chain, parameter) the moments s1 = sum (v - mid), s2 = sum (v - mid)^2 with mid = (lo + hi) / 2,
     per parameter a histogram of n_bins bins over [lo, hi] pooled over the chains (``outside``
@@ -483,7 +541,6 @@ class ChainSummary:
         self.counts = torch.zeros(*G, self.n_param, self.n_bins, dtype=torch.int64, device=dev)
         self.outside = torch.zeros(*G, self.n_param, dtype=torch.int64, device=dev)
         self.n_acc = torch.zeros(1, dtype=torch.int64, device=dev)
-        self._packed = None                        # event of a pack_behind the next accumulation waits for
         self.acf_state = self.acov = self.acf_n = None
         if self.acf_lags:
             size = int(ctx.lib.gs_chain_acf_state_size(self.n_group, self.n_chain, self.n_param, self.acf_lags))
@@ -494,11 +551,6 @@ class ChainSummary:
             self.acov = torch.zeros(self.n_group * self.n_param * (self.acf_lags + 1), dtype=torch.float64,
                                     device=dev)
             self.acf_n = torch.zeros(1, dtype=torch.int64, device=dev)
-
-    def _after_pack(self):
-        if self._packed is not None:
-            self.ctx.stream.wait_event(self._packed)
-            self._packed = None
 
     def accumulate(self, eng):
         """Add the engine's current state x (the row of sweep eng.it) for every chain."""
@@ -518,28 +570,17 @@ class ChainSummary:
         """Add rows [:n_rows] of x_block (rows, n_group * n_chain, n_param), the states before sweeps
         first_sweep, first_sweep + 1, ...: one launch on the context's stream.  The rows may be
         padded (any row stride >= a row); inside a row the block must be contiguous."""
-        if x_block.dim() != 3 or tuple(x_block.shape[1:]) != (self.n_group * self.n_chain, self.n_param):
-            raise ValueError(f"the summary holds {self.n_group} x {self.n_chain} chains of {self.n_param} "
-                             f"parameters, the block is {tuple(x_block.shape)}")
-        if x_block.dtype != torch.float64 or x_block.device != self.s1.device:
-            raise ValueError(f"the block must be float64 on {self.s1.device} (got {x_block.dtype} on "
-                             f"{x_block.device})")
-        row = self.n_group * self.n_chain * self.n_param
-        if not x_block[:1].is_contiguous() or (x_block.shape[0] > 1 and x_block.stride(0) < row):
-            raise ValueError(f"the block's rows must be contiguous and at least {row} apart (strides "
-                             f"{tuple(x_block.stride())})")
-        if not 0 <= int(n_rows) <= x_block.shape[0]:
-            raise ValueError(f"n_rows = {n_rows} of a block of {x_block.shape[0]} rows")
+        stride = self._check_block(x_block, self.n_param, n_rows, self.s1)
         self._after_pack()
         check(self.ctx.lib.gs_chain_summary_block(
             self.ctx.handle, self.n_group, self.n_chain, self.n_param, ptr(x_block[:1]), int(n_rows),
-            max(int(x_block.stride(0)), row), int(first_sweep), self.burn, self.n_bins, ptr(self.lo),
+            stride, int(first_sweep), self.burn, self.n_bins, ptr(self.lo),
             ptr(self.hi), ptr(self.scale), ptr(self.mid), ptr(self.s1), ptr(self.s2), ptr(self.counts),
             ptr(self.outside), ptr(self.n_acc)), "gs_chain_summary_block")
         if self.acf_lags:
             check(self.ctx.lib.gs_chain_acf_block(
                 self.ctx.handle, self.n_group, self.n_chain, self.n_param, ptr(x_block[:1]), int(n_rows),
-                max(int(x_block.stride(0)), row), int(first_sweep), self.burn, self.acf_lags, ptr(self.mid),
+                stride, int(first_sweep), self.burn, self.acf_lags, ptr(self.mid),
                 ptr(self.acf_state)), "gs_chain_acf_block")
 
     # the two buffers a HistoryStreamer carries for a summary: int64 words (as float64 bit
@@ -552,21 +593,6 @@ class ChainSummary:
         if self.acf_lags:
             shapes.append((k * (self.acf_lags + 1),))
         return shapes
-
-    def _acf_reduce(self, out, stream=None):
-        """gs_chain_acf_reduce into ``out`` (a flat device buffer of extra_shapes[2]), queued on
-        ``stream`` (default: the context's).  The state is read only."""
-        main = self.ctx.stream
-        other = stream is not None and stream is not main
-        if other:
-            self.ctx.set_stream(stream)
-        try:
-            check(self.ctx.lib.gs_chain_acf_reduce(
-                self.ctx.handle, self.n_group, self.n_chain, self.n_param, self.acf_lags, ptr(self.acf_state),
-                ptr(out), ptr(self.acf_n)), "gs_chain_acf_reduce")
-        finally:
-            if other:
-                self.ctx.set_stream(main)
 
     def finalize(self, stream=None, acov_out=None):
         """Device tensors reduced over the C chains (of each group), n = n_acc rows each: counts,
@@ -581,7 +607,10 @@ class ChainSummary:
         acov = {}
         if self.acf_lags:
             out = self.acov if acov_out is None else acov_out
-            self._acf_reduce(out, stream)
+            with self._queued_on(stream):          # the state is read only
+                check(self.ctx.lib.gs_chain_acf_reduce(
+                    self.ctx.handle, self.n_group, self.n_chain, self.n_param, self.acf_lags, ptr(self.acf_state),
+                    ptr(out), ptr(self.acf_n)), "gs_chain_acf_reduce")
             G = (self.n_group,) if self.n_group > 1 else ()
             acov = dict(acov=out.view(*G, self.n_param, self.acf_lags + 1))
         with torch.cuda.stream(stream or self.ctx.stream):
@@ -615,18 +644,6 @@ class ChainSummary:
             for i, name in enumerate(("mean", "var", "W", "Bn", "rhat")):
                 reals[i].copy_(f[name].view(-1))
 
-    def pack_behind(self, stream, ints, reals, acov=None):
-        """``pack`` on another stream (a streamer's side stream), ordered after what the context's
-        stream holds so far: the three dozen small kernels of finalize() then run beside the next
-        block's sweeps instead of in front of them.  The next accumulate / accumulate_block waits
-        for it on the device, so the accumulators it reads do not move under it."""
-        ready = torch.cuda.Event()
-        ready.record(self.ctx.stream)
-        stream.wait_event(ready)
-        self.pack(ints, reals, acov, stream=stream)
-        self._packed = torch.cuda.Event()
-        self._packed.record(stream)
-
     def unpack(self, ints, reals, acov=None):
         """Host arrays of what ``pack`` wrote (ints, reals, acov: the fetched host tensors)."""
         G = (self.n_group,) if self.n_group > 1 else ()
@@ -642,8 +659,17 @@ class ChainSummary:
             out["acov"] = acov.numpy().reshape(*G, self.n_param, self.acf_lags + 1).copy()
         return out
 
+    def summary_entries(self, host, g=0):
+        """Group g's part of a summary.npz from ``unpack``'s arrays: counts, outside, n, mean, var,
+        W, Bn and rhat, and with acf_lags what diagnostics.acf_summary derives from acov."""
+        one = self.n_group == 1
+        out = {k: v if one or k == "n" else v[g].copy() for k, v in host.items() if k != "acov"}
+        if "acov" in host:
+            out.update(acf_summary(host["acov"] if one else host["acov"][g].copy(), int(host["n"]), self.n_chain))
+        return out
 
-class CoefMoments:
+
+class CoefMoments(_BlockAccumulator):
     """Pooled mean and covariance of the recorded coefficients b of every chain, accumulated on the
     device (gs_coef_moments_block): one group per entry of ``m`` (a pulsar with m[g] <= ldb
     coefficients), ``n_chain`` chains each.  ``accumulate_block`` takes a block of recorded b rows;
@@ -651,7 +677,11 @@ class CoefMoments:
     (gs_coef_moments_reduce, which leaves it untouched) into n (n_group,), shift, mean
     (n_group, ldb) and cov (n_group, ldb, ldb) -- diagnostics.coef_moments restates them on the
     host; entries beyond m[g] are zero.  pack / pack_behind / unpack carry a save point's arrays in
-    three buffers of ``extra_shapes``, as ChainSummary's do."""
+    three buffers of ``extra_shapes``, as ChainSummary's do.  ``names`` (optional, set by the owner):
+    per group the labels of its coefficients, which ``summary_entries`` passes on as b_names."""
+
+    _holds = ("moments hold", "coefficients")
+    names = None
 
     def __init__(self, ctx, n_chain, m, ldb, burn=0):
         self.ctx, self.n_chain, self.ldb, self.burn = ctx, int(n_chain), int(ldb), int(burn)
@@ -673,30 +703,16 @@ class CoefMoments:
         self.n = torch.zeros(self.n_group, dtype=torch.int64, device=dev)
         self.shift_mean = torch.zeros(2, k, dtype=torch.float64, device=dev)
         self.cov = torch.zeros(k * self.ldb, dtype=torch.float64, device=dev)
-        self._packed = None                        # event of a pack_behind the next accumulation waits for
 
     def accumulate_block(self, b_block, first_sweep, n_rows):
         """Add rows [:n_rows] of b_block (rows, n_group * n_chain, ldb), the coefficients before
         sweeps first_sweep, first_sweep + 1, ...: queued on the context's stream.  The rows may be
         padded (any row stride >= a row); inside a row the block must be contiguous."""
-        if b_block.dim() != 3 or tuple(b_block.shape[1:]) != (self.n_group * self.n_chain, self.ldb):
-            raise ValueError(f"the moments hold {self.n_group} x {self.n_chain} chains of {self.ldb} "
-                             f"coefficients, the block is {tuple(b_block.shape)}")
-        if b_block.dtype != torch.float64 or b_block.device != self.state.device:
-            raise ValueError(f"the block must be float64 on {self.state.device} (got {b_block.dtype} on "
-                             f"{b_block.device})")
-        row = self.n_group * self.n_chain * self.ldb
-        if not b_block[:1].is_contiguous() or (b_block.shape[0] > 1 and b_block.stride(0) < row):
-            raise ValueError(f"the block's rows must be contiguous and at least {row} apart (strides "
-                             f"{tuple(b_block.stride())})")
-        if not 0 <= int(n_rows) <= b_block.shape[0]:
-            raise ValueError(f"n_rows = {n_rows} of a block of {b_block.shape[0]} rows")
-        if self._packed is not None:
-            self.ctx.stream.wait_event(self._packed)
-            self._packed = None
+        stride = self._check_block(b_block, self.ldb, n_rows, self.state)
+        self._after_pack()
         check(self.ctx.lib.gs_coef_moments_block(
             self.ctx.handle, self.n_group, self.n_chain, self.ldb, ptr(self.m), ptr(b_block[:1]), int(n_rows),
-            max(int(b_block.stride(0)), row), int(first_sweep), self.burn, ptr(self.state)),
+            stride, int(first_sweep), self.burn, ptr(self.state)),
             "gs_coef_moments_block")
 
     # the three buffers a HistoryStreamer carries for the moments: n (int64 words as float64 bit
@@ -709,17 +725,10 @@ class CoefMoments:
     def pack(self, ints, reals, cov, stream=None):
         """gs_coef_moments_reduce into three float64 buffers of ``extra_shapes`` (a streamer
         slot's), queued on ``stream`` (default: the context's).  The state is read only."""
-        main = self.ctx.stream
-        other = stream is not None and stream is not main
-        if other:
-            self.ctx.set_stream(stream)
-        try:
+        with self._queued_on(stream):
             check(self.ctx.lib.gs_coef_moments_reduce(
                 self.ctx.handle, self.n_group, self.n_chain, self.ldb, ptr(self.m), ptr(self.state),
                 ptr(ints), ptr(reals[0]), ptr(reals[1]), ptr(cov)), "gs_coef_moments_reduce")
-        finally:
-            if other:
-                self.ctx.set_stream(main)
 
     def finalize(self, stream=None):
         """Device tensors n, shift, mean, cov (the class's own buffers).  No host synchronisation."""
@@ -728,16 +737,6 @@ class CoefMoments:
         return dict(n=self.n, shift=self.shift_mean[0].view(G, ldb), mean=self.shift_mean[1].view(G, ldb),
                     cov=self.cov.view(G, ldb, ldb))
 
-    def pack_behind(self, stream, ints, reals, cov):
-        """``pack`` on another stream (a streamer's side stream), ordered after what the context's
-        stream holds so far; the next accumulate_block waits for it."""
-        ready = torch.cuda.Event()
-        ready.record(self.ctx.stream)
-        stream.wait_event(ready)
-        self.pack(ints, reals, cov, stream=stream)
-        self._packed = torch.cuda.Event()
-        self._packed.record(stream)
-
     def unpack(self, ints, reals, cov):
         """Host arrays of what ``pack`` wrote (the fetched host tensors), a leading group axis on
         each: n (G,) int64, shift, mean (G, ldb), cov (G, ldb, ldb)."""
@@ -745,6 +744,15 @@ class CoefMoments:
         r = reals.numpy()
         return dict(n=ints.numpy().view(np.int64).copy(), shift=r[0].reshape(G, ldb).copy(),
                     mean=r[1].reshape(G, ldb).copy(), cov=cov.numpy().reshape(G, ldb, ldb).copy())
+
+    def summary_entries(self, host, g=0):
+        """Group g's part of a summary.npz from ``unpack``'s arrays, cut to its m[g] coefficients:
+        [b_names,] b_n, b_shift, b_mean, b_cov."""
+        mg = int(self.m_host[g])
+        out = {} if self.names is None else dict(b_names=np.array(self.names[g]))
+        out.update(b_n=np.int64(host["n"][g]), b_shift=host["shift"][g, :mg].copy(),
+                   b_mean=host["mean"][g, :mg].copy(), b_cov=host["cov"][g, :mg, :mg].copy())
+        return out
 
 
 def grid3(rhomin, rhomax, n=1000, device="cuda"):

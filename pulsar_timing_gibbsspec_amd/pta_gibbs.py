@@ -31,7 +31,7 @@ from .engine import DeviceModel, PTAChains
 from .plumbing import (basis_layout, expand_names, flat_bounds, last_match, matching_indices, power_bounds,
                        vector_to_dict)
 from .pta_hyper import HYPER_WARMUP, HyperSpec, hyper_aclength
-from .pulsar_gibbs import HOST_CHAIN, resolve_seed, write_summary
+from .pulsar_gibbs import HOST_CHAIN, resolve_seed, summary_header, summary_options, write_summary
 
 
 class PTABlockGibbs(object):
@@ -348,15 +348,9 @@ class PTABlockGibbs(object):
         if history != "summary" and (bins != 64 or burn != 0):
             raise ValueError("bins and burn need history='summary'")
         if history == "summary":
-            for name, v, a, b in (("bins", bins, 1, 256), ("burn", burn, 0, int(niter) - 1)):
-                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not a <= v <= b:
-                    raise ValueError(f"{name} must be an integer in {a}..{b} (got {v!r})")
-            if resume:
-                raise NotImplementedError("resume=True is not wired for history='summary' (the accumulators are "
-                                          "not saved)")
+            summary = summary_options(bins, burn, niter, resume)     # record_chains: checked with thin below
             return self._sample_disk(xs, outdir, int(niter), False, int(save_every), flush_final,
-                                     1 if record_chains is None else record_chains, thin, slots,
-                                     summary=(int(bins), int(burn)))
+                                     1 if record_chains is None else record_chains, thin, slots, summary=summary)
         if history == "disk":
             return self._sample_disk(xs, outdir, int(niter), resume, int(save_every), flush_final,
                                      record_chains, thin, slots)
@@ -392,24 +386,7 @@ class PTABlockGibbs(object):
         ii = start
         seen_fail = 0
         if start > 0:
-            eng.it = start
-            if eng.hyper is not None and eng.hyper_acl is None:
-                if state is not None and "aclength_hyper" in state.files:
-                    eng.hyper_acl = int(state["aclength_hyper"])
-                else:
-                    raise NotImplementedError("resuming a redsample='mh' run needs aclength_hyper (set the "
-                                              "attribute, or keep gibbs_state.npz)")
-            if state is not None:
-                # the device state saved with these rows (gibbs_state.npz): the run continues
-                # exactly where the uninterrupted one would be
-                eng.x.copy_(torch.as_tensor(state["x"], device=dev))
-                eng.b.copy_(torch.as_tensor(state["b"], device=dev))
-            else:
-                # only chain.txt (e.g. written by the reference): as pta_gibbs.py:642-661,
-                # restart from the last row, which the next sweep records again -- but draw
-                # b | x first (the reference keeps b = 0 there, which makes tau = 0 and the
-                # grid CDF 0/0)
-                eng.redraw_b = True
+            self._restore(eng, start, state)
         while ii < niter:
             nxt = min(niter, (ii // save_every + 1) * save_every + 1)
             for j in range(nxt - ii):
@@ -417,12 +394,7 @@ class PTABlockGibbs(object):
             rows = buf[:nxt - ii].cpu().numpy()
             eng.check_fx()                             # curn_mode='sum': tau inside the fixed-point window
             nfail = int(eng.fail_count.sum())          # failed (non-PD) b draws, b kept
-            if nfail > seen_fail:
-                print(f"WARNING: sweeps {ii}..{nxt - 1}: {nfail - seen_fail} b draws hit a non-positive-definite "
-                      "Sigma; those systems KEEP their previous b -- unlike the reference, whose LinAlgError "
-                      "branch (pta_gibbs.py:539-544) redraws b from a QR/SVD of Sigma with the wrong covariance "
-                      "(SURVEY Appendix A.7)")
-                seen_fail = nfail
+            seen_fail = self._warn_failed(ii, nxt, nfail, seen_fail)
             self.chain[ii:nxt] = rows[:, 0]
             if nc > 1:
                 self.chains[:, ii:nxt] = np.moveaxis(rows, 1, 0)
@@ -442,6 +414,42 @@ class PTABlockGibbs(object):
             if nc > 1:
                 np.save(f"{outdir}/chains.npy", self.chains[:, :self.iter + 1])
             self._save_state(outdir, self.iter + 1, eng)
+        return self._read_back(eng)
+
+    def _restore(self, eng, start, state):
+        """A resumed run's engine at sweep ``start``.  state: what gibbs_state.npz held for these
+        rows, or None."""
+        dev = self.ctx.device
+        eng.it = start
+        if eng.hyper is not None and eng.hyper_acl is None:
+            if state is not None and "aclength_hyper" in state:
+                eng.hyper_acl = int(state["aclength_hyper"])
+            else:
+                raise NotImplementedError("resuming a redsample='mh' run needs aclength_hyper (set the "
+                                          "attribute, or keep gibbs_state.npz)")
+        if state is not None:
+            # the device state saved with these rows: the run continues exactly where the
+            # uninterrupted one would be
+            eng.x.copy_(torch.as_tensor(state["x"], device=dev))
+            eng.b.copy_(torch.as_tensor(state["b"], device=dev))
+        else:
+            # only chain.txt (e.g. written by the reference): as pta_gibbs.py:642-661, restart
+            # from the last row, which the next sweep records again -- but draw b | x first (the
+            # reference keeps b = 0 there, which makes tau = 0 and the grid CDF 0/0)
+            eng.redraw_b = True
+
+    @staticmethod
+    def _warn_failed(i0, i1, nfail, seen):
+        """Say so when sweeps i0..i1-1 raised the count of failed (non-PD) b draws; returns the count."""
+        if nfail > seen:
+            print(f"WARNING: sweeps {i0}..{i1 - 1}: {nfail - seen} b draws hit a non-positive-definite "
+                  "Sigma; those systems KEEP their previous b -- unlike the reference, whose LinAlgError "
+                  "branch (pta_gibbs.py:539-544) redraws b from a QR/SVD of Sigma with the wrong covariance "
+                  "(SURVEY Appendix A.7)")
+        return max(nfail, seen)
+
+    def _read_back(self, eng):
+        """What a finished run leaves on the sampler besides its chains; returns ``chain``."""
         b = eng.b.cpu().numpy()
         self._b = [b[p * eng.C, :eng.model.m[p]] for p in range(eng.P)]
         if eng.hyper is not None:
@@ -457,7 +465,7 @@ class PTABlockGibbs(object):
                      summary=None):
         """sample(history="disk"): see sample.  Blocks are the default mode's -- sweep 0, then
         (k S, (k + 1) S] for S = save_every, then the rest -- so save points and rows agree.
-        summary = (bins, burn): history="summary"."""
+        summary: the SummaryOptions of history="summary" (bins and burn; record_chains is the argument)."""
         from .chain_writer import ChainWriter
         from .engine import BlockRecorder, ChainSummary
         nc, npar, S = self.nchains, len(xs), save_every
@@ -505,7 +513,6 @@ class PTABlockGibbs(object):
         self.chains = writer.chains
         eng = self._new_engine(x0)
         self._engine = eng
-        dev = self.ctx.device
         # per block and slot: the chain-major rows, the state of a save point (x, b) and
         # [fx overflow flag, failed b draws so far]
         summ = None
@@ -513,7 +520,7 @@ class PTABlockGibbs(object):
             # every chain's posterior accumulated by the sweeps themselves; a block that ends at a
             # save point (or ends the run) carries the reduced arrays in two more buffers of its slot
             lo, hi = flat_bounds(self.params)
-            summ = ChainSummary(self.ctx, nc, npar, lo, hi, n_bins=summary[0], burn=summary[1])
+            summ = ChainSummary(self.ctx, nc, npar, lo, hi, n_bins=summary.bins, burn=summary.burn)
             self.summary = None
         rec = BlockRecorder(self.ctx, K, S // t, npar, thin=t, direct=slots == "host",
                             extra=[tuple(eng.x.shape), tuple(eng.b.shape), (2,)]
@@ -523,18 +530,7 @@ class PTABlockGibbs(object):
         ii = start
         seen_fail = 0
         if start > 0:
-            eng.it = start
-            if eng.hyper is not None and eng.hyper_acl is None:
-                if state is not None and "aclength_hyper" in state:
-                    eng.hyper_acl = int(state["aclength_hyper"])
-                else:
-                    raise NotImplementedError("resuming a redsample='mh' run needs aclength_hyper (set the "
-                                              "attribute, or keep gibbs_state.npz)")
-            if state is not None:
-                eng.x.copy_(torch.as_tensor(state["x"], device=dev))
-                eng.b.copy_(torch.as_tensor(state["b"], device=dev))
-            else:
-                eng.redraw_b = True            # as the default mode: draw b | x first
+            self._restore(eng, start, state)
 
         def drain(blk):
             """Fetch a launched block (waits for that block only), check it, file it."""
@@ -543,12 +539,7 @@ class PTABlockGibbs(object):
             rows, x_h, b_h, flags, *sum_h = st.fetch(slot)
             eng.check_fx(ovf=int(flags[0]))        # curn_mode='sum': tau inside the fixed-point window
             nfail = int(flags[1])                  # failed (non-PD) b draws, b kept
-            if nfail > seen_fail:
-                print(f"WARNING: sweeps {i0}..{i1 - 1}: {nfail - seen_fail} b draws hit a non-positive-definite "
-                      "Sigma; those systems KEEP their previous b -- unlike the reference, whose LinAlgError "
-                      "branch (pta_gibbs.py:539-544) redraws b from a QR/SVD of Sigma with the wrong covariance "
-                      "(SURVEY Appendix A.7)")
-                seen_fail = nfail
+            seen_fail = self._warn_failed(i0, i1, nfail, seen_fail)
             r0, r1 = -(-i0 // t), -(-i1 // t)      # the kept sweeps of [i0, i1)
             rows = rows.numpy()[:, :r1 - r0]
             self.chain[r0:r1] = rows[0]
@@ -565,9 +556,8 @@ class PTABlockGibbs(object):
                 writer.append(rows, commit=False)  # row 0 is filed with the first save point
             if summ is not None and (save or i1 == niter):
                 # rows [burn, last] of every chain, reduced on the device behind the block
-                self.summary = dict(names=np.array(self.param_names), lo=summ.lo_host, hi=summ.hi_host,
-                                    n_bins=np.int64(summ.n_bins), burn=np.int64(summ.burn), nchains=np.int64(nc),
-                                    rows=np.int64(i1), **summ.unpack(*sum_h))
+                self.summary = summary_header(self.param_names, summ, nc, i1)
+                self.summary.update(summ.unpack(*sum_h))
                 self._write_summary(outdir, self.summary)
 
         pending = None
@@ -609,9 +599,4 @@ class PTABlockGibbs(object):
         if pending is not None:
             drain(pending)
         writer.close()
-        b = eng.b.cpu().numpy()
-        self._b = [b[p * eng.C, :eng.model.m[p]] for p in range(eng.P)]
-        if eng.hyper is not None:
-            self.aclength_hyper = eng.hyper_acl
-            self.hyper_acceptance = eng.hyper.acceptance()
-        return self.chain
+        return self._read_back(eng)

@@ -34,12 +34,13 @@ Extensions (keyword-only, reference-equivalent defaults): ``nchains``
 from __future__ import annotations
 
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from .diagnostics import acf_summary, white_aclength
+from .diagnostics import white_aclength
 from .ecorr import EcorrFreeSpectrumChains, EcorrModel, EcorrWhiteChains
 from .engine import ChainSummary, CoefMoments, DeviceModel, FreeSpectrumChains, HistoryStreamer, check_handoff, grid3
 from .plumbing import (basis_layout, expand_names, flat_bounds, last_match, matching_indices, power_bounds,
@@ -86,25 +87,31 @@ def write_summary(outdir, summary):
     os.replace(tmp, f"{outdir}/summary.npz")
 
 
-def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume, acf_lags=None, b_moments=False):
-    """The history / bins / burn / record_chains / acf_lags / b_moments keywords of the
-    single-pulsar samplers, checked before anything is touched: None for history="memory", (bins,
-    burn, record_chains, acf_lags, b_moments) for history="summary" (acf_lags 0 when it was not
-    given)."""
-    if history not in ("memory", "summary"):
-        raise ValueError("history must be 'memory' or 'summary'")
-    if not isinstance(b_moments, (bool, np.bool_)):
-        raise ValueError(f"b_moments must be a bool (got {b_moments!r})")
-    if history != "summary":
-        if (bins is not None or burn is not None or record_chains is not None or acf_lags is not None
-                or b_moments):
-            raise ValueError("bins, burn, record_chains, acf_lags and b_moments need history='summary'")
-        return None
-    bins = 64 if bins is None else bins
-    burn = 0 if burn is None else burn
-    K = 1 if record_chains is None else record_chains
-    for name, v, a, b in (("bins", bins, 1, 256), ("burn", burn, 0, int(niter) - 1),
-                          ("record_chains", K, 1, int(nchains))):
+def summary_header(names, summ, nchains, rows):
+    """The keys every summary.npz starts with, in front of the accumulators' own (``summ``: the
+    engine.ChainSummary of the run; rows: the sweeps run so far)."""
+    return dict(names=np.array(names), lo=summ.lo_host, hi=summ.hi_host, n_bins=np.int64(summ.n_bins),
+                burn=np.int64(summ.burn), nchains=np.int64(nchains), rows=np.int64(rows))
+
+
+class SummaryOptions(NamedTuple):
+    """The checked keywords of a history="summary" run (acf_lags 0: none; record_chains None: the
+    sampler checks its own)."""
+    bins: int
+    burn: int
+    record_chains: Optional[int]
+    acf_lags: int
+    b_moments: bool
+
+
+def summary_options(bins, burn, niter, resume, record_chains=None, nchains=None, acf_lags=None, b_moments=False):
+    """SummaryOptions of a history="summary" run, checked before anything is touched: the ranges of
+    bins, burn and acf_lags, of record_chains when ``nchains`` is given, and the refusal of
+    resume."""
+    ranges = [("bins", bins, 1, 256), ("burn", burn, 0, int(niter) - 1)]
+    if nchains is not None:
+        ranges.append(("record_chains", record_chains, 1, int(nchains)))
+    for name, v, a, b in ranges:
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not a <= v <= b:
             raise ValueError(f"{name} must be an integer in {a}..{b} (got {v!r})")
     if acf_lags is not None:
@@ -116,7 +123,25 @@ def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume
     if resume:
         raise NotImplementedError("resume=True is not wired for history='summary' (the accumulators are "
                                   "not saved)")
-    return int(bins), int(burn), int(K), int(acf_lags or 0), bool(b_moments)
+    return SummaryOptions(int(bins), int(burn), None if nchains is None else int(record_chains),
+                          int(acf_lags or 0), bool(b_moments))
+
+
+def summary_arguments(history, bins, burn, record_chains, niter, nchains, resume, acf_lags=None, b_moments=False):
+    """The history / bins / burn / record_chains / acf_lags / b_moments keywords of the
+    single-pulsar samplers: None for history="memory", where none of the others may be given, else
+    summary_options with their defaults (64 bins, no burn, chain 0) filled in."""
+    if history not in ("memory", "summary"):
+        raise ValueError("history must be 'memory' or 'summary'")
+    if not isinstance(b_moments, (bool, np.bool_)):
+        raise ValueError(f"b_moments must be a bool (got {b_moments!r})")
+    if history != "summary":
+        if (bins is not None or burn is not None or record_chains is not None or acf_lags is not None
+                or b_moments):
+            raise ValueError("bins, burn, record_chains, acf_lags and b_moments need history='summary'")
+        return None
+    return summary_options(64 if bins is None else bins, 0 if burn is None else burn, niter, resume,
+                           1 if record_chains is None else record_chains, nchains, acf_lags, b_moments)
 
 
 def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_every, psr_base=0,
@@ -138,25 +163,29 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     b (the reference's bchain) is what the reference layout needs.  Without it only chain 0's
     b rows cross PCIe (the rest are recorded in HBM only).
 
-    summary = (bins, burn, record_chains, acf_lags, b_moments): history="summary".  The x rows of a block are recorded
-    into HBM slots; only chains 0..record_chains-1 of each pulsar go to the host (``chains`` is
-    (record_chains, niter, n_f), or None for one chain -- the (nchains, niter, n_f) array is never
-    allocated), and every chain's posterior is accumulated on the device behind each block
-    (engine.ChainSummary with one group per pulsar, gs_chain_summary_block; row ii is the state
-    before sweep ii, rows below ``burn`` are skipped).  At every save point and at the end the
-    arrays are reduced on the streamer's side stream (ChainSummary.pack_behind), travel in two
-    more buffers of the streamer's slot and are fetched one block behind, like the rows; each pulsar's summary.npz (the keys of PTABlockGibbs's) is rewritten
-    from them and kept as ``summary`` on its sampler.  b is recorded as in the default mode.
-    acf_lags = L > 0: gs_chain_acf_block follows the summary kernel behind each block, each
-    pulsar's pooled autocovariance up to lag L rides in a third extra buffer, and summary.npz gains
-    acf_lags, acov, iat, iat_window, ess_per_sweep, ess and ess_se (diagnostics.acf_summary; the
-    O(n_f L) window search stays on the host).  With acf_lags 0 nothing is added or launched.
-    b_moments (summary[4]): every chain's b rows are recorded into the slot's HBM buffer
-    (record_b_chains = nchains, never direct) and the streamer's view sends only the chains the run
-    without the keyword sends; engine.CoefMoments (gs_coef_moments_block, one group per pulsar)
-    follows the x summary behind each block, its reduced arrays ride in three more buffers, and
-    summary.npz gains b_names, b_n, b_shift, b_mean and b_cov (diagnostics.coef_moments).  Without
-    it no buffer, launch or key is added."""
+    summary (a SummaryOptions; None: history="memory"): history="summary".
+
+    * Rows.  The x rows of a block are recorded into HBM slots and only chains
+      0..record_chains-1 of each pulsar go to the host: ``chains`` is (record_chains, niter, n_f),
+      or None for one chain -- the (nchains, niter, n_f) array is never allocated.  b is recorded
+      as in the default mode.
+    * Accumulators.  Each one (engine.ChainSummary, and engine.CoefMoments with b_moments; one
+      group per pulsar) takes every block behind the sweeps (row ii is the state before sweep ii,
+      rows below ``burn`` are skipped on the device).  At every save point and at the end it is
+      reduced on the streamer's side stream (pack_behind) into buffers of its own in the
+      streamer's slot (its extra_shapes), which are fetched one block behind, like the rows.
+    * summary.npz.  Per pulsar: summary_header's keys, then each accumulator's summary_entries
+      -- with the ChainSummary alone the keys of PTABlockGibbs's file.  It is rewritten at each
+      of those points and kept as ``summary`` on the sampler.
+    * acf_lags = L > 0: gs_chain_acf_block follows the summary kernel behind each block, each
+      pulsar's pooled autocovariance up to lag L is one more buffer of the ChainSummary, and the
+      file gains acf_lags, acov, iat, iat_window, ess_per_sweep, ess and ess_se
+      (diagnostics.acf_summary; the O(n_f L) window search stays on the host).
+    * b_moments: every chain's b rows are recorded into the slot's HBM buffer (record_b_chains =
+      nchains, never direct), where gs_coef_moments_block reads them, and the streamer's view
+      sends only the chains that the run without the keyword sends.  The file gains b_names, b_n,
+      b_shift, b_mean and b_cov (diagnostics.coef_moments).
+    Without acf_lags or b_moments no buffer, launch or key of theirs is added."""
     P = len(samplers)
     nc = samplers[0].nchains
     ctx = model.ctx
@@ -168,7 +197,7 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
         record_bchains = nc <= 16
     allb = nc > 1 and bool(record_bchains)
     # chains whose x rows reach the host, and whether they are kept as ``chains`` / chains.npy
-    K = nc if summary is None else summary[2]
+    K = nc if summary is None else summary.record_chains
     multi = K > 1
     for s in samplers:
         s.chain = np.zeros((niter, n_f))
@@ -228,33 +257,39 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
     # straight into the pinned slots; every chain's b (record_bchains) goes through HBM and the
     # copy engine
     bk = bstride = nc if (allb or nc == 1) else 1      # chains of b recorded, and of those sent to the host
-    bmom = bsend = None
-    if summary is not None and summary[4]:
-        # b_moments: every chain's b rows into the slot's HBM buffer, where gs_coef_moments_block
-        # reads them; the copy engine takes the chains per pulsar that the host gets without it
-        bmom = CoefMoments(ctx, nc, m, model.ldb, burn=summary[1])
-        bk = nc
-        bsend = lambda t: t.view(t.shape[0], P, nc, model.ldb)[:, :, :bstride]   # noqa: E731
-    shapes = [(blk, P * nc, n_f), (blk, P * bk, model.ldb)]
-    summ = None
-    if summary is None:
-        streamer = HistoryStreamer(ctx, shapes, direct=[True, not allb])
-    else:
+    summ, views, direct = None, None, [True, not allb]
+    accs = []                  # (accumulator, the record buffer it reads: 0 the x rows, 1 the b rows)
+    if summary is not None:
         # x rows into HBM slots: the summary kernel reads them there, and the copy engine takes
-        # the first K chains of each pulsar; the reduced arrays of a save point ride in two more
-        # buffers of the slot, three with acf_lags (a leading axis of 1: the streamer slices rows)
+        # the first K chains of each pulsar
         lo, hi = flat_bounds(samplers[0].params)
-        summ = ChainSummary(ctx, nc, n_f, lo, hi, n_bins=summary[0], burn=summary[1], n_group=P,
-                            acf_lags=summary[3])
-        extra = [(1,) + tuple(e) for e in summ.extra_shapes]
-        n_sum = len(extra)                         # the summary's buffers; the moments' three follow
-        if bmom is not None:
-            extra += [(1,) + tuple(e) for e in bmom.extra_shapes]
-        keep = lambda t: t.view(t.shape[0], P, nc, n_f)[:, :, :K]   # noqa: E731
-        streamer = HistoryStreamer(ctx, shapes + extra, views=[keep, bsend] + [None] * len(extra),
-                                   direct=[False, not allb and bmom is None] + [False] * len(extra))
+        summ = ChainSummary(ctx, nc, n_f, lo, hi, n_bins=summary.bins, burn=summary.burn, n_group=P,
+                            acf_lags=summary.acf_lags)
+        accs.append((summ, 0))
+        views = [lambda t: t.view(t.shape[0], P, nc, n_f)[:, :, :K], None]
+        direct = [False, not allb]
+        if summary.b_moments:
+            # every chain's b rows into the slot's HBM buffer, where gs_coef_moments_block reads
+            # them; the copy engine takes the chains per pulsar that the host gets without it
+            bmom = CoefMoments(ctx, nc, m, model.ldb, burn=summary.burn)
+            bmom.names = [s.b_param_names for s in samplers]
+            accs.append((bmom, 1))
+            bk = nc
+            views[1] = lambda t: t.view(t.shape[0], P, nc, model.ldb)[:, :, :bstride]
+            direct[1] = False
         for s in samplers:
             s.summary = None
+    # the reduced arrays of a save point ride in further buffers of the slot, each accumulator's
+    # extra_shapes in turn (a leading axis of 1: the streamer slices rows)
+    extra = [(1,) + tuple(e) for a, _ in accs for e in a.extra_shapes]
+    streamer = HistoryStreamer(ctx, [(blk, P * nc, n_f), (blk, P * bk, model.ldb)] + extra,
+                               views=views and views + [None] * len(extra), direct=direct + [False] * len(extra))
+
+    def shares(bufs):
+        """A slot's extra buffers, dealt to the accumulators in the order they were laid out."""
+        it = iter(bufs)
+        return [[next(it)[0] for _ in a.extra_shapes] for a, _ in accs]
+
     # failed (non-PD) draws, surfaced per block as they happen: the kernels keep b and count
     # (gs_ctx_set_fail_counts); each block's counts reach pinned memory behind the block
     fc_host = [torch.zeros(P * nc, dtype=torch.int32, pin_memory=True) for _ in range(2)]
@@ -281,20 +316,11 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
         save = last % save_every == 0 and last > 0
         if summ is not None and (save or nxt == niter):
             # rows [burn, last] of every chain, reduced on the device behind the block
-            red = summ.unpack(*[h[0] for h in sum_h[:n_sum]])
-            acov = red.pop("acov", None)
-            bred = bmom.unpack(*[h[0] for h in sum_h[n_sum:]]) if bmom is not None else None
+            red = [a.unpack(*h) for (a, _), h in zip(accs, shares(sum_h))]
             for p, (s, o) in enumerate(zip(samplers, outdirs)):
-                s.summary = dict(names=np.array(s.param_names), lo=summ.lo_host, hi=summ.hi_host,
-                                 n_bins=np.int64(summ.n_bins), burn=np.int64(summ.burn), nchains=np.int64(nc),
-                                 rows=np.int64(nxt),
-                                 **{k: v if P == 1 or k == "n" else v[p].copy() for k, v in red.items()})
-                if acov is not None:
-                    s.summary.update(acf_summary(acov if P == 1 else acov[p].copy(), int(red["n"]), nc))
-                if bred is not None:
-                    s.summary.update(b_names=np.array(s.b_param_names), b_n=np.int64(bred["n"][p]),
-                                     b_shift=bred["shift"][p, :m[p]].copy(), b_mean=bred["mean"][p, :m[p]].copy(),
-                                     b_cov=bred["cov"][p, :m[p], :m[p]].copy())
+                s.summary = summary_header(s.param_names, summ, nc, nxt)
+                for (a, _), r in zip(accs, red):
+                    s.summary.update(a.summary_entries(r, p))
                 s._write_summary(o, s.summary)
         for p, (s, o) in enumerate(zip(samplers, outdirs)):
             xp = xh[:, p]
@@ -315,15 +341,12 @@ def sample_free_spectrum(samplers, model, xs_list, outdirs, niter, resume, save_
         n = nxt - ii
         xr, br, *sum_d = streamer.buffers(slot, n)
         runner.run(n, x_rec=xr, b_rec=br, record_b_chains=bk)
-        if summ is not None:
-            summ.accumulate_block(xr, ii, n)
-            if bmom is not None:
-                bmom.accumulate_block(br, ii, n)
-            if ((nxt - 1) % save_every == 0 and nxt > 1) or nxt == niter:
-                # reduced on the side stream, in front of the slot's copies and beside the next block
-                summ.pack_behind(streamer.side, *[d[0] for d in sum_d[:n_sum]])
-                if bmom is not None:
-                    bmom.pack_behind(streamer.side, *[d[0] for d in sum_d[n_sum:]])
+        for a, src in accs:
+            a.accumulate_block((xr, br)[src], ii, n)
+        if accs and (((nxt - 1) % save_every == 0 and nxt > 1) or nxt == niter):
+            # reduced on the side stream, in front of the slot's copies and beside the next block
+            for (a, _), d in zip(accs, shares(sum_d)):
+                a.pack_behind(streamer.side, *d)
         with torch.cuda.stream(ctx.stream):
             fc_host[slot].copy_(runner.fail_count, non_blocking=True)
             info_host[slot].copy_(runner.info, non_blocking=True)
@@ -916,22 +939,14 @@ class PulsarBlockGibbs(object):
         np.savetxt(f"{outdir}/pars_bchain.txt", self.b_param_names, fmt="%s")
 
         if self._red_loop():
-            out = self._sample_red(xs, outdir, niter, resume, save_every)
-            if flush_final:
-                self._flush(outdir)
-            return out
-        if self._ecorr_loop():
-            out = self._sample_ecorr(xs, outdir, niter, resume, save_every)
-            if flush_final:
-                self._flush(outdir)
-            return out
-        if self._white_loop():
-            out = self._sample_white(xs, outdir, niter, resume, save_every)
-            if flush_final:
-                self._flush(outdir)
-            return out
-        sample_free_spectrum([self], self._model(xs), [xs], [outdir], niter, resume, save_every,
-                             record_bchains=record_bchains, summary=summary)
+            self._sample_red(xs, outdir, niter, resume, save_every)
+        elif self._ecorr_loop():
+            self._sample_ecorr(xs, outdir, niter, resume, save_every)
+        elif self._white_loop():
+            self._sample_white(xs, outdir, niter, resume, save_every)
+        else:
+            sample_free_spectrum([self], self._model(xs), [xs], [outdir], niter, resume, save_every,
+                                 record_bchains=record_bchains, summary=summary)
         if flush_final:
             self._flush(outdir)
         return self.chain
@@ -946,21 +961,15 @@ class PulsarBlockGibbs(object):
         save_rows(self, outdir, self.iter + 1, self.chains is not None,
                   getattr(self, "bchains", None) is not None)
 
-    def _sample_white(self, xs, outdir, niter, resume, save_every):
-        """sample() with the white-noise MH block (pulsar_gibbs.py:656-698): one device
-        launch sequence per sweep for all chains (white.WhiteFreeSpectrumChains)."""
+    def _load_steps(self, n_param, outdir, niter, resume):
+        """The host arrays of a step-loop run (white, ECORR, red) and, on resume, the saved rows of
+        chain 0 (chain.npy, bchain.npy): returns the number of rows a resume starts from, else 0."""
         nc = self.nchains
-        dev = self.ctx.device
-        wm = self._white_model(xs, nc)
-        m = int(wm.m[0])
-        n_param = len(xs)
         self.chain = np.zeros((niter, n_param))
         self.bchain = np.zeros((niter, len(self._b)))
         self.chains = np.zeros((nc, niter, n_param)) if nc > 1 else None
         self.bchains = np.zeros((nc, niter, len(self._b))) if nc > 1 else None
         start = 0
-        x0 = np.asarray(xs, float)
-        acl = getattr(self, "aclength_white", None)
         if resume and os.path.exists(f"{outdir}/chain.npy"):
             print("Resuming from previous run...")
             c0 = np.load(f"{outdir}/chain.npy")
@@ -968,17 +977,21 @@ class PulsarBlockGibbs(object):
             start = min(c0.shape[0], b0.shape[0])
             self.chain[:start] = c0[:start]
             self.bchain[:start] = b0[:start]
-        runner = WhiteFreeSpectrumChains(wm, n_param, self.get_gwrho_param_indices(), self.rhomin,
-                                         self.rhomax, x0, aclength=acl)
+        return start
+
+    def _run_steps(self, runner, m, ldb, start, outdir, niter, save_every):
+        """Sweeps start .. niter-1 of ``runner`` (one ``sweep(x_rec, b_rec)`` each, b records ldb
+        wide with m coefficients) into the arrays of _load_steps, in blocks that end at the save
+        points.  A resume restarts every chain from chain 0's last saved row, which the next sweep
+        records again."""
+        nc, dev = self.nchains, self.ctx.device
         if start > 0:
             runner.x.copy_(torch.as_tensor(self.chain[start - 1][None, :], device=dev).expand(nc, -1))
             runner.b[:, :m] = torch.as_tensor(self.bchain[start - 1], device=dev)
             runner.it = start
-            if runner.aclength is None:
-                raise NotImplementedError("resume of a white-noise run needs aclength_white")
         blk = max(1, save_every)
-        xr = torch.empty(blk + 1, nc, n_param, dtype=torch.float64, device=dev)
-        br = torch.empty(blk + 1, nc, wm.ldb, dtype=torch.float64, device=dev)
+        xr = torch.empty(blk + 1, nc, self.chain.shape[1], dtype=torch.float64, device=dev)
+        br = torch.empty(blk + 1, nc, ldb, dtype=torch.float64, device=dev)
         ii = start
         while ii < niter:
             nxt = min(niter, (ii // blk + 1) * blk + 1)
@@ -993,10 +1006,22 @@ class PulsarBlockGibbs(object):
                 self.chains[:, ii:nxt] = np.moveaxis(xh, 1, 0)
                 self.bchains[:, ii:nxt] = np.moveaxis(bh, 1, 0)
             ii = nxt
-            self.iter = ii - 1
-            last = ii - 1
+            self.iter = last = ii - 1
             if last % save_every == 0 and last > 0:
                 save_rows(self, outdir, last + 1, nc > 1, nc > 1)
+        self._b = runner.b[0, :m].cpu().numpy()
+        self._runner = runner
+
+    def _sample_white(self, xs, outdir, niter, resume, save_every):
+        """sample() with the white-noise MH block (pulsar_gibbs.py:656-698): one device
+        launch sequence per sweep for all chains (white.WhiteFreeSpectrumChains)."""
+        wm = self._white_model(xs, self.nchains)
+        start = self._load_steps(len(xs), outdir, niter, resume)
+        runner = WhiteFreeSpectrumChains(wm, len(xs), self.get_gwrho_param_indices(), self.rhomin, self.rhomax,
+                                         np.asarray(xs, float), aclength=getattr(self, "aclength_white", None))
+        if start > 0 and runner.aclength is None:
+            raise NotImplementedError("resume of a white-noise run needs aclength_white")
+        self._run_steps(runner, int(wm.m[0]), wm.ldb, start, outdir, niter, save_every)
         if runner.short_chain is not None:
             sc = runner.short_chain
             self.cov_white = np.cov(sc[100:, :], rowvar=False)
@@ -1008,32 +1033,16 @@ class PulsarBlockGibbs(object):
         info = runner.info.cpu().numpy()
         if info.any():
             print(f"WARNING: {int((info != 0).sum())} chains hit a non-positive-definite Sigma")
-        self._b = runner.b[0, :m].cpu().numpy()
-        self._runner = runner
-        return self.chain
 
     def _sample_ecorr(self, xs, outdir, niter, resume, save_every):
         """sample() with the basis-ECORR MH block in the notebook sampler's order (ECORR
         block, rho|b, gated b; pulsar_gibbs.py:656-698 with :675-683 enabled): one device
         launch sequence per sweep for all chains (ecorr.EcorrFreeSpectrumChains)."""
         nc = self.nchains
-        dev = self.ctx.device
         white = self._ecorr_white()
         em = self._ecorr_model(xs, nc, per_chain=white)
-        m, n_param = em.m, len(xs)
-        self.chain = np.zeros((niter, n_param))
-        self.bchain = np.zeros((niter, len(self._b)))
-        self.chains = np.zeros((nc, niter, n_param)) if nc > 1 else None
-        self.bchains = np.zeros((nc, niter, len(self._b))) if nc > 1 else None
-        start = 0
+        start = self._load_steps(len(xs), outdir, niter, resume)
         x0 = np.asarray(xs, float)
-        if resume and os.path.exists(f"{outdir}/chain.npy"):
-            print("Resuming from previous run...")
-            c0 = np.load(f"{outdir}/chain.npy")
-            b0 = np.load(f"{outdir}/bchain.npy")
-            start = min(c0.shape[0], b0.shape[0])
-            self.chain[:start] = c0[:start]
-            self.bchain[:start] = b0[:start]
         if white:
             # both warm-ups (update_white_params / update_ecorr_params iters=1000, notebook
             # sample() at ii == 0) run once on the 1-chain device models from xs to set the
@@ -1051,33 +1060,9 @@ class PulsarBlockGibbs(object):
         else:
             runner = EcorrFreeSpectrumChains(em, self.get_gwrho_param_indices(), self.gwid, self.rhomin,
                                              self.rhomax, x0, aclength=getattr(self, "aclength_ecorr", None))
-        if start > 0:
-            if runner.aclength is None:
-                raise NotImplementedError("resume of an ECORR run needs aclength_ecorr")
-            runner.x.copy_(torch.as_tensor(self.chain[start - 1][None, :], device=dev).expand(nc, -1))
-            runner.b[:, :m] = torch.as_tensor(self.bchain[start - 1], device=dev)
-            runner.it = start
-        blk = max(1, save_every)
-        xr = torch.empty(blk + 1, nc, n_param, dtype=torch.float64, device=dev)
-        br = torch.empty(blk + 1, nc, m, dtype=torch.float64, device=dev)
-        ii = start
-        while ii < niter:
-            nxt = min(niter, (ii // blk + 1) * blk + 1)
-            n = nxt - ii
-            for k in range(n):
-                runner.sweep(x_rec=xr[k], b_rec=br[k])
-            xh = xr[:n].cpu().numpy()
-            bh = br[:n].cpu().numpy()
-            self.chain[ii:nxt] = xh[:, 0]
-            self.bchain[ii:nxt] = bh[:, 0]
-            if nc > 1:
-                self.chains[:, ii:nxt] = np.moveaxis(xh, 1, 0)
-                self.bchains[:, ii:nxt] = np.moveaxis(bh, 1, 0)
-            ii = nxt
-            self.iter = ii - 1
-            last = ii - 1
-            if last % save_every == 0 and last > 0:
-                save_rows(self, outdir, last + 1, nc > 1, nc > 1)
+        if start > 0 and runner.aclength is None:
+            raise NotImplementedError("resume of an ECORR run needs aclength_ecorr")
+        self._run_steps(runner, em.m, em.m, start, outdir, niter, save_every)
         if runner.short_chain is not None:
             sc = runner.short_chain
             self.cov_ecorr = np.cov(sc[100:, :], rowvar=False)
@@ -1086,69 +1071,24 @@ class PulsarBlockGibbs(object):
         self.aclength_ecorr = runner.aclength
         if int(em.binfo.max()) != 0:
             print("WARNING: chains hit a non-positive-definite Sigma")
-        self._b = runner.b[0, :m].cpu().numpy()
-        self._runner = runner
-        return self.chain
 
     def _sample_red(self, xs, outdir, niter, resume, save_every):
         """sample() with power-law red noise (pulsar_gibbs.py:656-698): sweep 0 runs the
         warm-up (update_red_params(iters=10000), :689-690) on the host with the device
         likelihood; every sweep is then one launch sequence for all chains
         (rednoise.RedNoiseChains)."""
-        nc = self.nchains
-        dev = self.ctx.device
-        n_param = len(xs)
         model = self._model(xs)
-        m = int(model.m[0])
-        self.chain = np.zeros((niter, n_param))
-        self.bchain = np.zeros((niter, len(self._b)))
-        self.chains = np.zeros((nc, niter, n_param)) if nc > 1 else None
-        self.bchains = np.zeros((nc, niter, len(self._b))) if nc > 1 else None
-        start = 0
+        start = self._load_steps(len(xs), outdir, niter, resume)
         x0 = np.asarray(xs, float)
-        if resume and os.path.exists(f"{outdir}/chain.npy"):
-            print("Resuming from previous run...")
-            c0 = np.load(f"{outdir}/chain.npy")
-            b0 = np.load(f"{outdir}/bchain.npy")
-            start = min(c0.shape[0], b0.shape[0])
-            self.chain[:start] = c0[:start]
-            self.bchain[:start] = b0[:start]
         x_first = None
         if start == 0 and getattr(self, "_red_jumps", None) is None:
             x_first = self.update_red_params(x0, iters=getattr(self, "red_warmup_iters", 10000))
         elif getattr(self, "_red_jumps", None) is None:
             raise NotImplementedError("resume of a red-noise run needs the warm-up's proposal (_red_jumps)")
-        runner = self._red_engine(x0, nc, x_first=x_first)
-        if start > 0:
-            runner.x.copy_(torch.as_tensor(self.chain[start - 1][None, :], device=dev).expand(nc, -1))
-            runner.b[:, :m] = torch.as_tensor(self.bchain[start - 1], device=dev)
-            runner.it = start
-        blk = max(1, save_every)
-        xr = torch.empty(blk + 1, nc, n_param, dtype=torch.float64, device=dev)
-        br = torch.empty(blk + 1, nc, model.ldb, dtype=torch.float64, device=dev)
-        ii = start
-        while ii < niter:
-            nxt = min(niter, (ii // blk + 1) * blk + 1)
-            n = nxt - ii
-            for k in range(n):
-                runner.sweep(x_rec=xr[k], b_rec=br[k])
-            xh = xr[:n].cpu().numpy()
-            bh = br[:n, :, :m].cpu().numpy()
-            self.chain[ii:nxt] = xh[:, 0]
-            self.bchain[ii:nxt] = bh[:, 0]
-            if nc > 1:
-                self.chains[:, ii:nxt] = np.moveaxis(xh, 1, 0)
-                self.bchains[:, ii:nxt] = np.moveaxis(bh, 1, 0)
-            ii = nxt
-            self.iter = ii - 1
-            last = ii - 1
-            if last % save_every == 0 and last > 0:
-                save_rows(self, outdir, last + 1, nc > 1, nc > 1)
+        runner = self._red_engine(x0, self.nchains, x_first=x_first)
+        self._run_steps(runner, int(model.m[0]), model.ldb, start, outdir, niter, save_every)
         info = runner.info.cpu().numpy()
         if info.any():
             print(f"WARNING: {int((info != 0).sum())} chains hit a non-positive-definite Sigma")
         steps = runner.n_blocks * runner.nsteps
         self.red_acceptance = (runner.acc_total.cpu().numpy() / steps) if steps else None
-        self._b = runner.b[0, :m].cpu().numpy()
-        self._runner = runner
-        return self.chain
