@@ -191,8 +191,11 @@ int gs_sweep_lds_bytes(int NF, int NMX);
 int gs_tnt(gs_ctx* ctx, int n_psr, int m_max, const gs_tnt_desc* desc,
            const double* T, const double* Nvec, const double* r, double* TNT, double* d);
 /*
- * Same in double-double: TNT + TNT_lo and d + d_lo equal T^T N^-1 T and T^T N^-1 r of the
- * fp64 inputs to ~1e-30 relative (exact products, compensated sums; TNT exactly symmetric).
+ * Same in double-double (exact products, compensated sums; TNT and TNT_lo exactly symmetric):
+ * per element, |TNT + TNT_lo - S| <= (n_toa + 16) 2^-104 M for S = sum_t T_ti T_tj / N_t of the
+ * fp64 inputs and M = sum_t |T_ti T_tj / N_t| -- relative to the sum of the terms' magnitudes,
+ * not to the result -- and TNT alone is within 1 ulp(S) + that; the same for d + d_lo with r_t
+ * in place of T_tj (asserted by tests/test_gpu_setup_shapes.py).
  * TNT_lo / d_lo may be NULL.  Feed the pairs to gs_prefix_dd: the fp64 rounding of TNT is,
  * relative to the Schur block the draw factorises, a perturbation of up to ~1e-9 at 10^4
  * TOAs.  VALU work; once per noise state.
